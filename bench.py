@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput bench of the GeoFormer matching path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--precision fp16|bf16|fp32]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--precision fp16|bf16|fp32] [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json configs[4], "batched inference, 1024 synthetic 640x640 pairs, fp16 features, 8 GPUs
 embarrassingly-parallel shard"): the pair list (seeds 0 .. N*K*B-1) is cut into contiguous per-rank blocks
@@ -19,6 +19,12 @@ K ~ 1200, reported in `config` because cost scales with them).  `--pairs homogra
 Launching: `--gpus N` (N > 1) without a launcher starts the N ranks ITSELF (fresh child processes, before anything
 in the parent touches the GPU), waits for them and relays rank 0's line; under `python -m torch.distributed.run`
 (RANK / LOCAL_RANK / WORLD_SIZE in the environment) it is one of the ranks.  `--gpus` must equal the world size.
+
+A plain run sets up, warms up, times ONE region of K steps and prints the headline line (`value`, `ms_per_step`, the
+shard plan, the match counts).  `--full` adds everything else the line has carried: two more timed regions (`repeats`),
+the HIP-event kernel figures of the timed region and of a single-stream replay (`roofline`, `roofline_kernels`), the host
+enqueue time, the side measurements (other loads, precisions and shapes, the training step) and the CPU baseline.
+`--dump-outputs DIR` writes what the last timed step returned to its caller as DIR/<key>.npy (see output_arrays).
 
 One JSON line on rank 0 (see README / DESIGN.md for the fields).
 """
@@ -82,18 +88,26 @@ def parse_args(argv=None):
     ap.add_argument('--tune', action='store_true', help='let MIOpen search its convolution algorithms (minutes)')
     ap.add_argument('--save-db', action='store_true', help='with --tune: copy the searched find-db over geoformer_amd/miopen_db')
     ap.add_argument('--graphs', action='store_true', help='replay the static part of the forward from a captured hipGraph (GeoFormer.enable_graphs)')
-    ap.add_argument('--repeats', type=int, default=3,
+    ap.add_argument('--repeats', type=int, default=None,
                     help='timed regions of K steps each: the FIRST is `value` (W warm-up steps, then exactly K timed steps); the others '
-                         'follow it back to back and only feed the min / median / max of `repeats` in the line')
+                         'follow it back to back and only feed the min / median / max of `repeats` in the line (default: 3 with --full, else 1)')
     ap.add_argument('--independent', action='store_true',
                     help="with --pairs planted: feed the matching path the planted maps WITHOUT the data dependency on that step's backbone "
                          'output (rounds 3\'s headline; now the side measurement nominal_independent)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='skip the nominal-load and fp32 parity-mode side measurements')
-    ap.add_argument('--no-train', action='store_true', help='skip the training-step side measurement (BASELINE configs[2] / [3])')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline: repeats, per-kernel / roofline figures, host enqueue time, side measurements and the CPU '
+                         'baseline (the --no-* options below trim this set)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write what the last timed step returned as DIR/<key>.npy (float32 / float64; a fixed sample of large arrays)")
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip the side measurements')
+    ap.add_argument('--no-train', action='store_true', help='with --full: skip the training-step side measurement (BASELINE configs[2] / [3])')
     ap.add_argument('--dry-run', action='store_true',
                     help='launcher / rendezvous / shard plan only, on CPU over gloo (what tests/test_bench_launcher.py runs)')
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -401,6 +415,7 @@ class Pipelines:
         self.jobs = [queue.Queue() for _ in range(nstreams)]
         self.done = queue.Queue()
         self.results = {}
+        self.keep, self.kept = None, None          # the step index whose whole output is held for --dump-outputs, and that output
         self.serial = False
         self.pool = [threading.Thread(target=self._worker, args=(w,), daemon=True) for w in range(nstreams)]
         for t in self.pool:
@@ -410,6 +425,8 @@ class Pipelines:
         # keep the counts and the small geometry summary only: holding every step's output (two 1.3 GB confidence
         # matrices each) made the timed steps hipMalloc fresh memory - up to 3.5x the step time on a fresh box
         self.results[i] = (len(out['b_ids']), len(out['mkpts0_f']), out.get('_geo_dev', {}).get('nidx'))
+        if i == self.keep:
+            self.kept = out
 
     def _worker(self, w):
         torch = self.torch
@@ -506,11 +523,13 @@ def planted_step(model, i0, i1, pl, dependent):
 
 
 def measure(model, batches, steps, warmup, nstreams, dev, dist, log, profile_tag=None, L=None, planted=None, dependent=True,
-            repeats=1, pipes=None):
+            repeats=1, pipes=None, keep=None):
     """W untimed + K timed steps of `model` over the resident `batches`; returns (elapsed_s, pipelines, step_fn, repeat_times).
     planted = per-batch {'c': [2N,256,h,w], 'f': [2N,128,4h,4w]} (image-0 maps, then image-1 maps): the backbone runs on the
     images and the matching path is fed the planted feature maps, through the backbone's output when `dependent`.
     repeats > 1: further timed regions of K steps each behind the first (which alone is `elapsed_s`).
+    keep: called with the output of the first region's last step right after that region (before any repeat: the output holds its
+    step's buffers).
     pipes: host pipelines of an earlier measurement to reuse (same threads, streams, per-stream workspaces, MIOpen handles and
     allocator pools: a SECOND set of pipelines measured ~10 % slower than the first in the same process, whatever it ran)."""
     import torch
@@ -561,6 +580,8 @@ def measure(model, batches, steps, warmup, nstreams, dev, dist, log, profile_tag
         # around all ~110 profiled launches per step were seen to slow a whole run 3.5x on some boxes
         L.gf_profile_filter(profile_tag)
         L.gf_profile_enable(1)
+    if keep is not None:
+        pipes.keep = warmup + steps - 1
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     pipes.run(warmup, steps)
@@ -571,6 +592,9 @@ def measure(model, batches, steps, warmup, nstreams, dev, dist, log, profile_tag
     elapsed = time.perf_counter() - t0
     if profile_tag is not None:
         L.gf_profile_enable(0)                       # the in-region k1_conf figure belongs to the headline region only
+    if keep is not None:
+        keep(pipes.kept)
+        pipes.keep = pipes.kept = None
     times = [elapsed]
     for r in range(1, repeats):                      # the same K steps again, bracketed the same way; not part of `value`
         if dist is not None:
@@ -609,6 +633,40 @@ def load_pmc(path, run_cfg):
         src = f'{os.path.relpath(f, ROOT)} (separate rocprofv3 --pmc passes of this configuration, recorded {d.get("_recorded", "?")}; not this run)'
         return {k: v for k, v in d.items() if not k.startswith('_')}, src
     return {}, None
+
+
+DUMP_SAMPLE = 1 << 20            # elements: a larger output is dumped as this many elements at fixed flat indices
+DUMP_MAX_BYTES = 64 << 20
+
+
+def output_arrays(out):
+    """What one step returned to its caller, as host arrays for --dump-outputs: every tensor of the output dict except the inputs
+    (image0 / image1) and the internal '_' keys.  fp64 stays fp64, the other floating types become fp32, integers and booleans fp64
+    (exact).  An output of more than DUMP_SAMPLE elements (the two [B, L, S] confidence matrices, 328 M elements each at the default
+    shape, and fine_matrix) is reduced to DUMP_SAMPLE elements at flat indices drawn from a seed-0 generator: the same elements in every run."""
+    import torch
+    arrays = {}
+    for k, v in out.items():
+        if k.startswith('_') or k in ('image0', 'image1') or not torch.is_tensor(v):
+            continue
+        t = v.detach()
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randint(t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0))
+            t = t.reshape(-1)[idx.to(t.device)]
+        t = t.float() if t.is_floating_point() and t.dtype != torch.float64 else t.double()
+        arrays[k] = t.cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f'bench.py: --dump-outputs would write {total / 2**20:.1f} MB (at most {DUMP_MAX_BYTES >> 20} MB)')
+    return arrays
+
+
+def dump_outputs(arrays, path, log):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + '.npy'), a)
+    log(f'--dump-outputs: {len(arrays)} arrays, {sum(a.nbytes for a in arrays.values()) / 2**20:.1f} MB in {path}')
 
 
 def host_launch_us(model, batches, planted):
@@ -714,9 +772,13 @@ def main(argv=None):
         log(f'backbone {bb_ms:.2f} ms/pair after the search')
 
     dependent = not args.independent
-    elapsed, pipes, step, rep_times = measure(model, batches, args.steps, args.warmup, args.streams, dev, dist, log, b'k1_conf', L, planted,
-                                              dependent, max(1, args.repeats))
+    dumped = []
+    keep = (lambda out: dumped.append(output_arrays(out))) if args.dump_outputs and rank == 0 else None
+    elapsed, pipes, step, rep_times = measure(model, batches, args.steps, args.warmup, args.streams, dev, dist, log,
+                                              b'k1_conf' if args.full else None, L, planted, dependent, max(1, args.repeats), keep=keep)
     log('timed region done')
+    if dumped:
+        dump_outputs(dumped.pop(), args.dump_outputs, log)
     nstreams = 1 if pipes.serial else pipes.n
     res_rows = [pipes.results[i] for i in range(args.warmup, args.warmup + args.steps)]
     Ms, Mfs = [r[0] for r in res_rows], [r[1] for r in res_rows]
@@ -726,20 +788,22 @@ def main(argv=None):
         ms, cnt, work = ctypes.c_double(0), ctypes.c_int(0), ctypes.c_double(0)
         L.gf_profile_collect(tag.encode(), ctypes.byref(ms), ctypes.byref(cnt), ctypes.byref(work))
         return ms.value, cnt.value, work.value
-    timed_conf = collect('k1_conf')
-    L.gf_profile_filter(None)
-    # Per-kernel durations for the roofline entries: with several host pipelines the HIP-event span of a launch
-    # also covers kernels of the other streams that share the GPU, so the same steps are replayed on ONE stream
-    # right after the timed region (same inputs, same code, profiling events on every tagged launch) and those
-    # uncontended durations are reported - they are what `rocprofv3 --kernel-trace -- python3 bench.py --streams 1`
-    # (profiles/) shows per kernel.  k1_conf's in-region average is kept next to it.
-    replay_steps = min(2, args.steps)
-    for i in range(replay_steps):
-        step(i)
-    torch.cuda.synchronize()
-    solo = {tag: collect(tag) for tag, _, _, _ in ROOFLINE_TAGS}
-    L.gf_profile_enable(0)
-    host_us = host_launch_us(model, batches, planted)
+    host_us = None
+    if args.full:
+        timed_conf = collect('k1_conf')
+        L.gf_profile_filter(None)
+        # Per-kernel durations for the roofline entries: with several host pipelines the HIP-event span of a launch
+        # also covers kernels of the other streams that share the GPU, so the same steps are replayed on ONE stream
+        # right after the timed region (same inputs, same code, profiling events on every tagged launch) and those
+        # uncontended durations are reported - they are what a `--streams 1` kernel trace of the bench
+        # (profiles/) shows per kernel.  k1_conf's in-region average is kept next to it.
+        replay_steps = min(2, args.steps)
+        for i in range(replay_steps):
+            step(i)
+        torch.cuda.synchronize()
+        solo = {tag: collect(tag) for tag, _, _, _ in ROOFLINE_TAGS}
+        L.gf_profile_enable(0)
+        host_us = host_launch_us(model, batches, planted)
     own_times = [float(v) for v in rep_times]                   # this rank's own regions (before the MAX over ranks)
     if dist is not None:
         t = torch.tensor(rep_times, device=dev, dtype=torch.float64)
@@ -757,41 +821,42 @@ def main(argv=None):
         return
 
     pairs = args.batch * args.steps * world
-    Lc = (args.size // 8) ** 2
-    e = 4 if args.precision == 'fp32' else 2
-    algo_bytes = args.batch * (2 * Lc * 256 * e + Lc * Lc * 4)     # per k1_conf launch (170.4 MB/pair-call at e=2)
-    if solo['k1_conf'][1]:
-        assert abs(solo['k1_conf'][2] / solo['k1_conf'][1] - algo_bytes) < 1.0
     run_cfg = {'precision': args.precision, 'batch': args.batch, 'size': args.size, 'pairs': args.pairs,
                'coarse_thr': args.coarse_thr, 'fine_thr': args.fine_thr}
-    pmc, pmc_src = load_pmc(args.pmc_file, run_cfg)
     entries = []
     K = int(nidx[:, 0].float().mean()) if nidx is not None else None
-    for tag, bound, hot, what in ROOFLINE_TAGS:
-        tot_ms, cnt, work = solo[tag]
-        if cnt == 0 or tot_ms <= 0:
-            continue
-        if tag == 'k4_self_attention':            # key counts are device-side: 4 L K C flops per image, 2 images per pair
-            work = cnt * 4.0 * (2 * args.batch) * Lc * (K or 0) * 256
-        peak = HBM_PEAK_GBPS if bound == 'hbm' else MFMA_PEAK_TFLOPS[args.precision]
-        ach = work / (tot_ms * 1e-3) / (1e9 if bound == 'hbm' else 1e12)
-        p = pmc.get(tag, {})
-        entries.append({'kernel': f'{tag}: {what}', 'tag': tag, 'bound': bound, 'hot_path': hot, 'achieved': ach, 'peak': peak,
-                        'unit': 'GB/s' if bound == 'hbm' else 'TFLOP/s', 'frac': ach / peak,
-                        'traffic': p.get('hbm_bytes_per_launch'), 'mfma_util_pmc': p.get('mfma_util'),
-                        'traffic_source': pmc_src if p else None,
-                        'launches': cnt, 'launches_per_step': cnt / replay_steps, 'avg_launch_ms': tot_ms / cnt,
-                        'total_ms_per_step': tot_ms / replay_steps,
-                        ('algorithmic_bytes_per_launch' if bound == 'hbm' else 'algorithmic_flops_per_launch'): work / cnt})
-    # the dominant kernel = the hot-path tag with the largest time per step (k1_unit spans k1_stats + k1_conf: not a kernel)
-    hot_entries = [x for x in entries if x['hot_path'] and x['tag'] != 'k1_unit']
-    dominant = dict(max(hot_entries, key=lambda x: x['total_ms_per_step'])) if hot_entries else {}
-    dominant['measured'] = ('HIP events on the launch stream; single-stream replay of the timed steps (equals the kernel '
-                            'durations of a --streams 1 rocprofv3 trace, profiles/)')
-    if timed_conf[1]:
-        for x in entries:
-            if x['tag'] == 'k1_conf':
-                x['avg_launch_ms_in_timed_region'] = timed_conf[0] / timed_conf[1]
+    if args.full:
+        Lc = (args.size // 8) ** 2
+        e = 4 if args.precision == 'fp32' else 2
+        algo_bytes = args.batch * (2 * Lc * 256 * e + Lc * Lc * 4)     # per k1_conf launch (170.4 MB/pair-call at e=2)
+        if solo['k1_conf'][1]:
+            assert abs(solo['k1_conf'][2] / solo['k1_conf'][1] - algo_bytes) < 1.0
+        pmc, pmc_src = load_pmc(args.pmc_file, run_cfg)
+        for tag, bound, hot, what in ROOFLINE_TAGS:
+            tot_ms, cnt, work = solo[tag]
+            if cnt == 0 or tot_ms <= 0:
+                continue
+            if tag == 'k4_self_attention':            # key counts are device-side: 4 L K C flops per image, 2 images per pair
+                work = cnt * 4.0 * (2 * args.batch) * Lc * (K or 0) * 256
+            peak = HBM_PEAK_GBPS if bound == 'hbm' else MFMA_PEAK_TFLOPS[args.precision]
+            ach = work / (tot_ms * 1e-3) / (1e9 if bound == 'hbm' else 1e12)
+            p = pmc.get(tag, {})
+            entries.append({'kernel': f'{tag}: {what}', 'tag': tag, 'bound': bound, 'hot_path': hot, 'achieved': ach, 'peak': peak,
+                            'unit': 'GB/s' if bound == 'hbm' else 'TFLOP/s', 'frac': ach / peak,
+                            'traffic': p.get('hbm_bytes_per_launch'), 'mfma_util_pmc': p.get('mfma_util'),
+                            'traffic_source': pmc_src if p else None,
+                            'launches': cnt, 'launches_per_step': cnt / replay_steps, 'avg_launch_ms': tot_ms / cnt,
+                            'total_ms_per_step': tot_ms / replay_steps,
+                            ('algorithmic_bytes_per_launch' if bound == 'hbm' else 'algorithmic_flops_per_launch'): work / cnt})
+        # the dominant kernel = the hot-path tag with the largest time per step (k1_unit spans k1_stats + k1_conf: not a kernel)
+        hot_entries = [x for x in entries if x['hot_path'] and x['tag'] != 'k1_unit']
+        dominant = dict(max(hot_entries, key=lambda x: x['total_ms_per_step'])) if hot_entries else {}
+        dominant['measured'] = ('HIP events on the launch stream; single-stream replay of the timed steps (equals the kernel '
+                                'durations of a --streams 1 rocprofv3 trace, profiles/)')
+        if timed_conf[1]:
+            for x in entries:
+                if x['tag'] == 'k1_conf':
+                    x['avg_launch_ms_in_timed_region'] = timed_conf[0] / timed_conf[1]
     tot_M, tot_Mf, tot_steps = (sum(r[k] for r in rows) for k in range(3))
     res = {
         'metric': 'image-pairs/sec (640x640)', 'value': pairs / elapsed, 'unit': 'image-pairs/s',
@@ -826,10 +891,9 @@ def main(argv=None):
                    'inlier_cells_per_pair': K, 'parallelism': f'pair-shard x{world} (no collective)',
                    'host_pipelines_per_gpu': nstreams, 'hip_graphs': bool(args.graphs),
                    'backbone_dependency': bool(dependent) if args.pairs == 'planted' else True, **run_cfg},
-        'host_launch_us_per_step': host_us,
-        'roofline': dominant,
-        'roofline_kernels': entries,
     }
+    if args.full:
+        res.update({'host_launch_us_per_step': host_us, 'roofline': dominant, 'roofline_kernels': entries})
     # the correlation sweep's figures as top-level scalars (north_star: achieved HBM GB/s on the correlation sweep): a parser that keeps
     # only scalar keys sees them too
     for x in entries:
@@ -837,12 +901,13 @@ def main(argv=None):
             res[f"{x['tag']}_frac"] = x['frac']
             res[f"{x['tag']}_us_per_launch"] = 1e3 * x['avg_launch_ms']
             res[f"{x['tag']}_achieved_{'GBps' if x['bound'] == 'hbm' else 'TFLOPs'}"] = x['achieved']
-    if world == 1 and not args.no_extras:
+    extras = args.full and world == 1 and not args.no_extras
+    if extras:
         res['side_measurements'] = side_measurements(args, model, dev, log, L, batches, planted, pipes)
         ind = res['side_measurements'].get('nominal_independent')
         if ind:                                   # what the two extra elementwise passes of the dependency cost the headline
             res['side_measurements']['dependency_cost_pct'] = 100.0 * (ind['value'] - res['value']) / ind['value']
-    if world == 1 and not args.no_extras:
+    if extras:
         del model, batches, planted
         torch.cuda.empty_cache()
         res['side_measurements']['hpatches_b1'] = hpatches_b1_measurements(dev, log, L, pipes if pipes.n == 2 and not pipes.serial else None)
@@ -852,12 +917,12 @@ def main(argv=None):
                 res[f'hpatches_b1_{k}'] = hb[k]
         model = batches = planted = None
     pipes.close()
-    if world == 1 and not args.no_extras and not args.no_train:
+    if extras and not args.no_train:
         torch.cuda.empty_cache()
         res['side_measurements']['train_step'] = train_measurements(dev, log)
         for k, v in res['side_measurements']['train_step'].items():      # top-level scalars as well
             res[f'train_{k}_pairs_per_s'], res[f'train_{k}_ms_per_step'] = v['value'], v['ms_per_step']
-    if not args.no_cpu_baseline and world == 1:          # reported on rank 0 at N = 1 only
+    if args.full and not args.no_cpu_baseline and world == 1:          # reported on rank 0 at N = 1 only
         res['cpu_baseline'] = cpu_baseline(W, args.coarse_thr, args.fine_thr, args.size, args.pairs)
     print(json.dumps(res), flush=True)
     if args.tune and args.save_db:

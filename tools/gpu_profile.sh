@@ -14,7 +14,7 @@ OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 cd $ROOT
-BENCH="python3 bench.py --streams 1 --no-cpu-baseline --no-extras $*"
+BENCH="python3 bench.py --full --streams 1 --no-cpu-baseline --no-extras $*"
 echo "== kernel trace: $BENCH"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_trace -o run -- $BENCH --steps 10 --warmup 3 > $OUT/${TAG}_trace.json 2> $OUT/${TAG}_trace.err
 echo "rc=$?"
