@@ -1039,7 +1039,10 @@ __global__ __launch_bounds__(NT, 2) void k1_stats_panel(K1Args a) {
                 cs0 = fmaf(e0, fcol[r], cs0);
                 cs1 = fmaf(e1, fcol[r], cs1);
             }
-            if (__any(kappa - fminf(c20, c21) > LAZY)) {                 // a 'deep' tile: column sums against their own maxima
+            // a 'deep' tile: column sums against their own maxima.  Also taken while the lane's references span more than 126: then some
+            // fcol = exp2(ref - kappa) is below the normal range, v_exp_f32 flushes it to 0, and a column maximum up to 64 above such a
+            // reference (no rescale) would drop out of the cached-factor sum
+            if (__any(kappa - fminf(c20, c21) > LAZY || kappa - minref > 126.f)) {
                 cs0 = 0.f; cs1 = 0.f;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {

@@ -650,26 +650,27 @@ def geoformer_forward(P, data, loftr_cfg=None, geo_cfg=None, homography_fn: Call
 K4_DEFER_LOG2 = 8.0      # geoformer_amd/csrc/k4_attention.hip:K4_DEFER
 
 
-def _flash_self_attention(q, k, v, st, tile: int = 32):
+def _flash_self_attention(q, k, v, st, tile: int = 32, defer: float = K4_DEFER_LOG2):
     """q [L,H,D], k, v [K,H,D] (rounded) -> [L,H,D]: online softmax over key tiles exactly as attn_self runs it in the 16-bit
     modes (round 5) - the softmax scale lives in the query operand, q' = round(q * log2(e) / sqrt(D)) to the storage type, so the
     logits x = q' . k are the exponent's log2 argument; a reference m per query that starts at the first tile's maximum and then
     moves up only when a tile's maximum exceeds it by more than 8 (the kernel's deferred maximum, a per-query rule);
     probabilities 2^(x - m) rounded to the storage type for the P.V product while their sum stays fp32, rescale by 2^(m_old - m_new)
     where m moved, one division at the end.  (Mathematically the reference's softmax(QK^T / sqrt(D)) V, geo_attention.py:72-101,
-    whatever the threshold; the one extra rounding is that of q * c.  With st = float32 nothing is rounded.)"""
+    whatever the threshold; the one extra rounding is that of q * c.  With st = float32 nothing is rounded.)  `defer` is the
+    threshold in log2 units (0: the reference moves with every new maximum); tensors on any device."""
     L, H, D = q.shape
     K = k.shape[0]
     c = math.log2(math.e) / D ** .5
     qs = rt(q * c, st)
-    m = torch.zeros(L, H)
-    l = torch.zeros(L, H)
-    o = torch.zeros(L, H, D)
+    m = q.new_zeros(L, H)
+    l = q.new_zeros(L, H)
+    o = q.new_zeros(L, H, D)
     for t0 in range(0, K, tile):
         kt, vt = k[t0:t0 + tile], v[t0:t0 + tile]
         x = torch.einsum('lhd,shd->lhs', qs, kt)          # log2 units
         tmax = x.max(dim=2)[0] - m
-        need = (tmax > K4_DEFER_LOG2) if t0 > 0 else torch.ones_like(tmax, dtype=torch.bool)
+        need = (tmax > defer) if t0 > 0 else torch.ones_like(tmax, dtype=torch.bool)
         d = torch.where(need, tmax, torch.zeros_like(tmax))
         alpha = torch.exp2(-d) if t0 > 0 else torch.zeros_like(d)      # first tile: O = l = 0
         m = m + d
