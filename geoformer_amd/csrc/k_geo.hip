@@ -61,7 +61,11 @@ __global__ void window_geometry(WgArgs a) {
     for (int k = 0; k < ww; ++k) {
         const float qx = px + (float)(k % a.wsz - half) * sx;      // x fastest (common_utils.py:71-78)
         const float qy = py + (float)(k / a.wsz - half) * sy;
-        const bool oob = (qx < 0.f) | (qy < 0.f) | (qx >= (float)a.Wimg) | (qy >= (float)a.Himg);   // on floats (:84)
+        // on floats (:84), written as "not inside" so that a NaN coordinate (a non-finite matrix, 0 * inf, inf / inf) is out of bounds
+        // by construction: for finite coordinates this is the reference's predicate; for NaN the reference's four comparisons are
+        // all false - an in-bounds mask with an unspecified integer from .long() - which cannot be reproduced and is not: such an
+        // entry is -1 here.  Every entry of the table is therefore -1 or a cell of the key grid, whatever the matrix.
+        const bool oob = !(qx >= 0.f && qy >= 0.f && qx < (float)a.Wimg && qy < (float)a.Himg);
         const long ix = oob ? 0 : (long)qx, iy = oob ? 0 : (long)qy;                                  // .long() (:89)
         if (a.kps) {
             a.kps[(((size_t)n * L + l) * ww + k) * 2] = (int32_t)ix;

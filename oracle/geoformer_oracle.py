@@ -366,7 +366,10 @@ def warp_points(points: torch.Tensor, hmat: torch.Tensor) -> torch.Tensor:
 def make_windows(kps: torch.Tensor, img_hw, window_size: int, scale):
     """kps [L,2] float -> (kps [L,ww,2] int64, mask [L,ww] bool).  Offsets (c-2, r-2)*scale with
     x fastest (:71-78); OOB test on the float coordinates (:84); OOB entries zeroed then .long()
-    (:88-89)."""
+    (:88-89).
+    A NaN coordinate (non-finite homography) fails all four comparisons, so this - like the reference - reports it
+    IN bounds with whatever integer .long() makes of NaN.  The HIP kernel deviates on purpose: it masks such an entry
+    (window cell -1), see k_geo.hip:window_geometry; finite coordinates are treated identically."""
     h, w = img_hw
     r = torch.arange(window_size) - window_size // 2
     dy, dx = torch.meshgrid(r, r, indexing='ij')
