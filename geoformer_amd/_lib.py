@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('GF_LIB_PATH') or os.path.join(_HERE, 'libgeoformer_hip.so')   # GF_LIB_PATH: A/B timing of two builds (tools/)
 
 GF_F32, GF_F16, GF_BF16 = 0, 1, 2
+GF_IMAGE_U8, GF_IMAGE_F32_NORMALISED, GF_IMAGE_F32_NORMALISED_RCP = 0, 1, 2      # gf_image_kind
 
 c_void_p, c_int, c_float, c_size_t = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 c_long, c_uint32 = ctypes.c_long, ctypes.c_uint32
@@ -123,6 +124,7 @@ SIGNATURES = {
     'gf_fine_match': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p,
                               c_void_p, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                               c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'gf_image_gray_resize': (c_int, [c_void_p, c_int, c_int, c_int, ctypes.c_longlong, c_void_p, c_int, c_int, c_int, c_void_p]),
 }
 
 

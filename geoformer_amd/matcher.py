@@ -91,8 +91,10 @@ def cv2_resize_linear_u8(src, wt, ht):
     return np.clip(out, 0, 255).astype(np.uint8)
 
 
-def load_gray_image(im_path):
-    """[H,W] uint8 like cv2.imread(im_path, cv2.IMREAD_GRAYSCALE) (data_io.py:50).
+def load_image_u8(im_path):
+    """The decoder half of `load_gray_image`: uint8 [H,W,3] RGB that still needs the fixed-point gray conversion
+    (`cv2_gray_u8` on the host, or the device kernel behind `ops.image_gray_resize`), or uint8 [H,W] that is final already
+    (the JPEG luma plane, mode 'L' files).
     PNG / PPM / BMP colour files (HPatches is PPM): OpenCV decodes BGR and applies its fixed-point BGR2GRAY - `cv2_gray_u8`,
     byte for byte.  JPEG (the FIRE / ISC evaluation images): OpenCV hands IMREAD_GRAYSCALE to libjpeg as
     out_color_space = JCS_GRAYSCALE, i.e. the decoder emits the Y plane of the file's YCbCr data itself and no RGB image ever
@@ -106,13 +108,67 @@ def load_gray_image(im_path):
         if im.mode == 'L':
             return np.array(im, dtype=np.uint8)
     if im.mode in ('RGB', 'RGBA', 'P', 'CMYK', 'YCbCr'):
-        return cv2_gray_u8(np.array(im.convert('RGB'), dtype=np.uint8))
+        return np.array(im.convert('RGB'), dtype=np.uint8)
     return np.array(im.convert('L'), dtype=np.uint8)
 
 
-def load_gray_scale_tensor(im_path, device, imsize=None, dfactor=8, value_to_scale=min, aspan=False):
+def load_gray_image(im_path):
+    """[H,W] uint8 like cv2.imread(im_path, cv2.IMREAD_GRAYSCALE) (data_io.py:50): `load_image_u8` + `cv2_gray_u8` where the
+    decoder returned colour."""
+    im = load_image_u8(im_path)
+    return cv2_gray_u8(im) if im.ndim == 3 else im
+
+
+class _Staging:
+    """Pinned host buffers for the uploads of preprocess='device', one per (device, slot), grown on demand and reused: no
+    per-image pin_memory() allocation.  A pair uploads two images before anything synchronises, so each image of a pair has its
+    own slot; an event recorded behind every copy is waited for before the slot's bytes are overwritten (it has long
+    completed in a matching loop, whose result download synchronises the stream)."""
+
+    def __init__(self):
+        self.slots = {}
+
+    def upload(self, im, device, slot=0):
+        """numpy uint8 image -> device tensor of the same shape, copied asynchronously on the current stream."""
+        device = torch.device(device)
+        if device.index is None:
+            device = torch.device('cuda', torch.cuda.current_device())
+        key = (device.index, slot)
+        buf, ev = self.slots.get(key, (None, None))
+        if ev is not None:
+            ev.synchronize()
+        if buf is None or buf.numel() < im.size:
+            buf = torch.empty(max(im.size, 1 << 20), dtype=torch.uint8).pin_memory()
+            ev = torch.cuda.Event()
+            self.slots[key] = (buf, ev)
+        host = buf[:im.size].view(im.shape)
+        host.numpy()[...] = im
+        with torch.cuda.device(device):
+            dev = host.to(device, non_blocking=True)
+            ev.record()
+        return dev
+
+
+_staging = _Staging()
+PREPROCESS = ('host', 'device')
+
+
+def load_gray_scale_tensor(im_path, device, imsize=None, dfactor=8, value_to_scale=min, aspan=False, preprocess='host', slot=0):
     """[1,1,H,W] float in [0,1] + (wo/wt, ho/ht); H, W multiples of dfactor (load_gray_scale_tensor_cv, data_io.py:48-62:
-    gray uint8 image -> cv2.resize on the uint8 image -> to_tensor)."""
+    gray uint8 image -> cv2.resize on the uint8 image -> to_tensor).
+    preprocess='host': gray conversion and resize in numpy, the fp32 image is uploaded.  preprocess='device': the decoded
+    uint8 bytes go to the device through the pinned staging buffer `slot` and one kernel (ops.image_gray_resize) does gray,
+    resize and the division - the same bits; callers that upload several images before they synchronise give each its own slot."""
+    if preprocess not in PREPROCESS:
+        raise ValueError(f'preprocess must be one of {PREPROCESS}, got {preprocess!r}')
+    if preprocess == 'device':
+        if torch.device(device).type != 'cuda':
+            raise ValueError(f"preprocess='device' runs on the GPU: it needs a cuda device, got device={device!r} (use preprocess='host')")
+        im = load_image_u8(im_path)
+        ho, wo = im.shape[:2]
+        wt, ht, scale = resize_im(wo, ho, imsize=imsize, dfactor=dfactor, value_to_scale=value_to_scale, aspan=aspan)
+        with torch.cuda.device(device):
+            return ops.image_gray_resize(_staging.upload(im, device, slot), wt, ht, reciprocal=True), scale       # the host path's `/ 255.0` on a GPU
     im = load_gray_image(im_path)
     ho, wo = im.shape
     wt, ht, scale = resize_im(wo, ho, imsize=imsize, dfactor=dfactor, value_to_scale=value_to_scale, aspan=aspan)
@@ -123,10 +179,16 @@ def load_gray_scale_tensor(im_path, device, imsize=None, dfactor=8, value_to_sca
 
 class GeoFormerMatcher:
     def __init__(self, imsize, match_threshold, no_match_upscale=False, ckpt=None, device='cuda', precision='fp32',
-                 miopen_search=False):
-        """precision / miopen_search are additions: 'fp16' is the fast mode; miopen_search=True lets MIOpen search its
+                 miopen_search=False, preprocess='host'):
+        """precision / miopen_search / preprocess are additions: 'fp16' is the fast mode; miopen_search=True lets MIOpen search its
         convolution algorithms once per new image shape (seconds each, ~25 % faster backbone afterwards: 6.8 -> 5.2 ms
-        per 480x640 pair) - worth it when a dataset repeats a few shapes."""
+        per 480x640 pair) - worth it when a dataset repeats a few shapes; preprocess='device' moves gray conversion, resize and
+        normalisation of the decoded images from numpy to one kernel per image (load_gray_scale_tensor), same bits."""
+        if preprocess not in PREPROCESS:
+            raise ValueError(f'preprocess must be one of {PREPROCESS}, got {preprocess!r}')
+        if preprocess == 'device' and torch.device(device).type != 'cuda':
+            raise ValueError(f"preprocess='device' runs on the GPU: it needs a cuda device, got device={device!r} (use preprocess='host')")
+        self.preprocess = preprocess
         from . import miopen
         miopen.use_shipped_find_db()              # no-op if the caller configured MIOpen already
         if miopen_search:
@@ -148,8 +210,9 @@ class GeoFormerMatcher:
         self.model = self.model.eval().to(device)
         self.name = f'GeoFormer_{self.ckpt_name}' + ('_noms' if no_match_upscale else '')
 
-    def load_im(self, im_path):
-        return load_gray_scale_tensor(im_path, self.device, imsize=self.imsize, dfactor=8, value_to_scale=min)
+    def load_im(self, im_path, slot=0):
+        return load_gray_scale_tensor(im_path, self.device, imsize=self.imsize, dfactor=8, value_to_scale=min,
+                                      preprocess=self.preprocess, slot=slot)
 
     def match_inputs_(self, gray1, gray2):
         with torch.no_grad():
@@ -159,8 +222,8 @@ class GeoFormerMatcher:
         return np.concatenate([kpts1, kpts2], axis=1), kpts1, kpts2, scores
 
     def match_pairs(self, im1_path, im2_path):
-        gray1, sc1 = self.load_im(im1_path)
-        gray2, sc2 = self.load_im(im2_path)
+        gray1, sc1 = self.load_im(im1_path, slot=0)
+        gray2, sc2 = self.load_im(im2_path, slot=1)        # its own staging buffer: the first upload may still be in flight
         upscale = np.array([sc1 + sc2])
         matches, kpts1, kpts2, scores = self.match_inputs_(gray1, gray2)
         if self.no_match_upscale:
@@ -279,8 +342,8 @@ def eval_hpatches(matcher, data_root, ransac_thres=3, thres=(1, 3, 5, 10), scale
 
 # ---------------------------------------------------------------------------------------------
 # command line: the counterparts of `python inference.py` and `python eval_Hpatches.py`
-#   python -m geoformer_amd.matcher match im1 im2 [--ckpt saved_ckpt/geoformer.ckpt] [--out matches.npz]
-#   python -m geoformer_amd.matcher hpatches /path/to/hpatches-sequences-release [--ckpt ...]
+#   python -m geoformer_amd.matcher match im1 im2 [--ckpt saved_ckpt/geoformer.ckpt] [--out matches.npz] [--preprocess device]
+#   python -m geoformer_amd.matcher hpatches /path/to/hpatches-sequences-release [--ckpt ...] [--preprocess device]
 # ---------------------------------------------------------------------------------------------
 def main(argv=None):
     """Defaults follow the reference per sub-command: `match` = inference.py:107 (imsize 640, matches scaled back to the
@@ -308,6 +371,9 @@ def main(argv=None):
         p.add_argument('--precision', choices=('fp32', 'fp16', 'bf16'), default='fp16',
                        help="fp16 / bf16 = the fast modes (16-bit storage, fp32 accumulation; bf16 = BASELINE configs[1]'s wording); "
                             "fp32 = the reference's arithmetic")
+        p.add_argument('--preprocess', choices=PREPROCESS, default='host',
+                       help='where the decoded images are converted to gray, resized and normalised: numpy on the host, or one HIP kernel '
+                            'per image on the device (bit-identical output)')
     args = ap.parse_args(argv)
     world = int(os.environ.get('WORLD_SIZE', '1'))
     local = int(os.environ.get('LOCAL_RANK', '0'))
@@ -315,7 +381,7 @@ def main(argv=None):
         torch.cuda.set_device(local)
         torch.distributed.init_process_group('nccl', device_id=torch.device('cuda', local))
     matcher = GeoFormerMatcher(args.imsize, args.match_threshold, args.no_match_upscale, args.ckpt, device=f'cuda:{local}',
-                               precision=args.precision)
+                               precision=args.precision, preprocess=args.preprocess)
     if args.cmd == 'match':
         res = matcher(args.im1, args.im2)
         print(f'{matcher.name}: {len(res[0])} matches')

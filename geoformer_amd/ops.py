@@ -153,6 +153,35 @@ def pos_encode(x, pe_hwc, out_dtype, out=None):
     return out
 
 
+def image_gray_resize(src_u8, wt, ht, out=None, normalised=True, reciprocal=False):
+    """Image preprocessing in one launch: decoded uint8 image -> gray -> resize to (wt, ht) -> [1,1,ht,wt] fp32 in [0,1]
+    (normalised=False: the resized gray image itself, [ht,wt] uint8).  Bit-identical to matcher.cv2_resize_linear_u8(
+    cv2_gray_u8(src), wt, ht) and to that image / 255.0 in torch: the correctly rounded quotient, as torch divides on the CPU, or
+    with reciprocal=True the product with fp32(1 / 255), as torch's device kernel computes `t / 255.0` (it turns a Python-scalar
+    divisor into a multiplication; last-bit differences for 126 of the 256 byte values) - the bits of matcher's host path on a GPU.
+    src_u8: CUDA uint8 [H,W,3] (RGB) or [H,W] (already gray), pixels contiguous, any row stride (a crop needs no copy).
+    out: optional destination holding ht*wt contiguous elements of the result's dtype, e.g. one [1,ht,wt] slice of an
+    [N,1,ht,wt] batch: images of different source sizes are assembled into a batch without a cat."""
+    _need_cuda(src_u8, out)
+    if src_u8.dtype != torch.uint8 or src_u8.dim() not in (2, 3) or (src_u8.dim() == 3 and src_u8.shape[2] != 3):
+        raise ValueError(f'image_gray_resize: src_u8 must be a uint8 [H,W,3] or [H,W] tensor, got {src_u8.dtype} {tuple(src_u8.shape)}')
+    ch = 3 if src_u8.dim() == 3 else 1
+    hs, ws = src_u8.shape[:2]
+    wt, ht = int(wt), int(ht)
+    if hs < 1 or ws < 1 or (ch == 3 and src_u8.stride(2) != 1) or (ws > 1 and src_u8.stride(1) != ch) or (hs > 1 and src_u8.stride(0) < ws * ch):
+        raise ValueError('image_gray_resize: the pixels of a source row must be contiguous (row stride >= W * channels)')
+    dtype = torch.float32 if normalised else torch.uint8
+    if out is None:
+        out = torch.empty(ht, wt, dtype=dtype, device=src_u8.device)
+    elif out.dtype != dtype or out.numel() != ht * wt or not out.is_contiguous() or out.device != src_u8.device:
+        raise ValueError(f'image_gray_resize: out must hold {ht} x {wt} contiguous {dtype} elements on {src_u8.device}')
+    stride = src_u8.stride(0) if hs > 1 else ws * ch
+    kind = _lib.GF_IMAGE_U8 if not normalised else _lib.GF_IMAGE_F32_NORMALISED_RCP if reciprocal else _lib.GF_IMAGE_F32_NORMALISED
+    check(_lib.lib().gf_image_gray_resize(_p(src_u8), ch, hs, ws, stride, _p(out), kind,
+                                          ht, wt, ctypes.c_void_p(_stream_handle(src_u8.device))), 'gf_image_gray_resize')
+    return out.view(1, 1, ht, wt) if normalised else out.view(ht, wt)
+
+
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
 
 

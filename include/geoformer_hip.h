@@ -505,6 +505,24 @@ int gf_fine_match(const void* f0, const void* f1, int dtype, int M, int WW, int 
                   float* fine_matrix, float* mkpts0_f, float* mkpts1_f, float* mconf, int64_t* m_bids,
                   int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Image preprocessing: decoded uint8 image -> gray -> resize -> the tensor the model consumes, one launch
+ * replaces load_gray_scale_tensor_cv (eval_tool/immatch/utils/data_io.py:48-62): cv2.imread(IMREAD_GRAYSCALE),
+ *          cv2.resize on the uint8 image (default INTER_LINEAR), to_tensor
+ *   src  uint8 [hs, ws, channels], channels = 3 (RGB interleaved: gray = (R*4899 + G*9617 + B*1868 + 2^13) >> 14) or 1
+ *        (already gray), rows src_row_stride_bytes apart (>= ws * channels: a crop or a padded image needs no copy);
+ *   dst  dense [ht, wt]: GF_IMAGE_U8 = the resized gray image; GF_IMAGE_F32_NORMALISED = that image / 255 in fp32, the correctly rounded
+ *        quotient (torch's `t / 255.0` on the CPU); GF_IMAGE_F32_NORMALISED_RCP = that image * fp32(1 / 255), which is what torch's DEVICE
+ *        kernel computes for `t / 255.0` (a Python-scalar divisor becomes a multiplication by the rounded reciprocal there) and so what
+ *        matcher.load_gray_scale_tensor's host path hands the model on a GPU; the two differ in the last bit for 126 of the 256 byte values.
+ *   ws == wt and hs == ht: gray only;  ws == 2 wt and hs == 2 ht: (a + b + c + d + 2) >> 2;  otherwise OpenCV's 8-bit fixed-point bilinear
+ *   (11-bit weights computed on the device from (d + 0.5) * size_ratio - 0.5 in fp64, unfused).  Bit-identical to
+ *   geoformer_amd.matcher.cv2_resize_linear_u8(cv2_gray_u8(src), wt, ht).  No workspace.
+ * ------------------------------------------------------------------------------------------ */
+typedef enum { GF_IMAGE_U8 = 0, GF_IMAGE_F32_NORMALISED = 1, GF_IMAGE_F32_NORMALISED_RCP = 2 } gf_image_kind;
+int gf_image_gray_resize(const void* src, int channels, int hs, int ws, long long src_row_stride_bytes, void* dst, int dst_kind,
+                         int ht, int wt, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
