@@ -5,7 +5,6 @@ Objects are cached per source under csrc/_obj keyed on content hashes, so rebuil
 recompiles only what changed.
 """
 import hashlib
-import re
 import os
 import subprocess
 import sys
@@ -40,8 +39,6 @@ def _file_flags(body):
 def _compile(src, hdig, verbose):
     body = open(src, 'rb').read()
     extra = _file_flags(body)
-    for inc in re.findall(rb'#include "([\w.]+\.hip)"', body):       # a source that includes another one is rebuilt with it
-        body += open(os.path.join(CSRC, inc.decode()), 'rb').read()
     tag = hashlib.sha256(body + hdig.encode()).hexdigest()[:16]
     obj = os.path.join(OBJ, os.path.basename(src) + '.' + tag + '.o')
     if not os.path.exists(obj):

@@ -176,6 +176,23 @@ __device__ __forceinline__ int gf_acc_row(int r, int h) { return (r & 3) + 8 * (
 __device__ __forceinline__ int gf_lds_off(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
 
 // ---------------------------------------------------------------------------------------------
+// LDS-DMA: 64 lanes x 16 B from a buffer straight into 1 KiB of LDS at dst, no registers.  Issued as buffer_load_dwordx4 ... lds
+// (MUBUF) rather than global_load_lds: behind a FLAT-encoded LDS-DMA the compiler's wait insertion turns every LDS counter wait
+// into lgkmcnt(0) while a request is pending (it may touch both address spaces) - which is always, in a kernel that streams;
+// behind the MUBUF form the waits stay counted.  Scalar descriptor + 32-bit offsets: no 64-bit address arithmetic per piece, and a
+// lane whose offset is outside the buffer's range gets ZEROS in LDS (tools/probes/lds_dma_oob.hip).
+// ---------------------------------------------------------------------------------------------
+struct GfRsrc {
+    __amdgpu_buffer_rsrc_t r;
+};
+__device__ __forceinline__ GfRsrc gf_rsrc(const void* p, unsigned bytes) {
+    return GfRsrc{__builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000)};
+}
+__device__ __forceinline__ void gf_lds_dma(const GfRsrc& rs, char* dst, int voffset, int soffset = 0) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs.r, (__attribute__((address_space(3))) void*)dst, 16, voffset, soffset, 0, 0);
+}
+
+// ---------------------------------------------------------------------------------------------
 // cross-lane reduce-scatter over the 32 lanes of each wave half, entirely on the VALU (no LDS
 // round trips: the ds_bpermute form measured ~60 dependent LDS latencies per call).
 // In: v[q], q = 0..31 (a per-lane array of partials for 32 "slots").  Out: lane c (= lane&31)

@@ -83,23 +83,11 @@ struct ConvGeo {
     static_assert(LDS <= 160 * 1024, "LDS budget");
 };
 
-// LDS-DMA as buffer_load_dwordx4 ... lds (MUBUF) rather than global_load_lds: behind a FLAT-encoded LDS-DMA the compiler's wait
-// insertion turns every LDS counter wait into lgkmcnt(0) while the request is pending (it may touch both address spaces) - i.e.
-// always, here; behind the MUBUF form it counts.  Scalar descriptor + 32-bit offsets: no 64-bit address arithmetic per piece,
-// and a lane whose offset is outside the buffer's range gets ZEROS in LDS (tools/probes/lds_dma_oob.hip): out-of-image halo
-// pixels need no page of zeros and no pointer select.
-struct ConvRsrc {
-    __amdgpu_buffer_rsrc_t r;
-};
-__device__ __forceinline__ ConvRsrc conv_rsrc(const void* p, unsigned bytes) {
-    return ConvRsrc{__builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000)};
-}
-__device__ __forceinline__ void conv_lds_dma(const ConvRsrc& rs, char* dst, int voffset, int soffset) {      // 64 lanes x 16 B -> 1 KiB at dst
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs.r, (__attribute__((address_space(3))) void*)dst, 16, voffset, soffset, 0, 0);
-}
+// Weights and pixel patches arrive by LDS-DMA (gf_lds_dma); a lane whose offset is outside the buffer's range gets zeros in LDS, so
+// out-of-image halo pixels need no page of zeros and no pointer select.
 // request weight block b of the stream into ring slot `slot`; the waves share its fragments round-robin
 template <int NT, int NW, bool S2 = false>
-__device__ __forceinline__ void conv_dma_block(const ConvRsrc& ws, char* smem, int b, int slot, int wave, int lane, int i0 = 0, int i1 = 1 << 20) {
+__device__ __forceinline__ void conv_dma_block(const GfRsrc& ws, char* smem, int b, int slot, int wave, int lane, int i0 = 0, int i1 = 1 << 20) {
     using G = ConvGeo<NT, NW, false, S2>;
     asm volatile("" : "+v"(lane));      // (as in conv_dma_patch)
     char* dst = smem + G::W10_OFF + slot * G::WBLK;
@@ -109,13 +97,13 @@ __device__ __forceinline__ void conv_dma_block(const ConvRsrc& ws, char* smem, i
     for (int i = 0; i < (G::FR + NW - 1) / NW; ++i) {
         const int f = wave + NW * i;
         // (f < FR holds for every wave where NW (i + 1) <= FR: no scalar branch for those pieces)
-        if (i >= i0 && i < i1 && (NW * (i + 1) <= G::FR || f < G::FR)) conv_lds_dma(ws, dst + f * C10_FRAG, lane * 16, b * G::WBLK + f * C10_FRAG);
+        if (i >= i0 && i < i1 && (NW * (i + 1) <= G::FR || f < G::FR)) gf_lds_dma(ws, dst + f * C10_FRAG, lane * 16, b * G::WBLK + f * C10_FRAG);
     }
 }
 
 // request the halo patch of (tile, channel chunk c) into patch buffer `buf`: pieces of 16 pixels x 64 B over the waves
 template <typename T, int CIN, int NT, int NW>
-__device__ __forceinline__ void conv_dma_patch(const ConvArgs& a, const ConvRsrc& xs, char* smem, int buf, int n, int y0, int x0, int c, int wave,
+__device__ __forceinline__ void conv_dma_patch(const ConvArgs& a, const GfRsrc& xs, char* smem, int buf, int n, int y0, int x0, int c, int wave,
                                                int lane, int i0 = 0, int i1 = 1 << 20) {
     using G = ConvGeo<NT, NW>;
     asm volatile("" : "+v"(lane));      // recompute the per-lane source offsets here: hoisted out of the K loop they cost
@@ -132,7 +120,7 @@ __device__ __forceinline__ void conv_dma_patch(const ConvArgs& a, const ConvRsrc
             const bool in = (unsigned)(y0 - 1 + pr) < (unsigned)a.Hi && (unsigned)(x0 - 1 + pc) < (unsigned)a.Wi && q < G::PH * PW;
             int off = (sbase + (pr * a.Wi + pc) * CIN + 8 * slot) * (int)sizeof(T);
             asm volatile("" : "+v"(off));       // (computed for every lane: left to the compiler the select becomes an exec-masked branch per piece)
-            conv_lds_dma(xs, dst + piece * 1024, in ? off : 0x7FFFFFF0, 0);                // outside the image: out of range -> zeros
+            gf_lds_dma(xs, dst + piece * 1024, in ? off : 0x7FFFFFF0, 0);                // outside the image: out of range -> zeros
         }
     }
 }
@@ -140,7 +128,7 @@ __device__ __forceinline__ void conv_dma_patch(const ConvArgs& a, const ConvRsrc
 // stride 2: request parity plane `plane` = (row parity, column parity) of the halo patch of (tile at OUTPUT pixel (y0, x0), channel chunk c):
 // plane pixel (pr, pc) = input pixel (2 (y0 + pr) - 1 + plane / 2, 2 (x0 + pc) - 1 + plane % 2); pieces of 16 plane pixels x 64 B
 template <typename T, int CIN, int NT, int NW>
-__device__ __forceinline__ void conv_dma_plane(const ConvArgs& a, const ConvRsrc& xs, char* smem, int plane, int n, int y0, int x0, int c, int wave,
+__device__ __forceinline__ void conv_dma_plane(const ConvArgs& a, const GfRsrc& xs, char* smem, int plane, int n, int y0, int x0, int c, int wave,
                                                int lane) {
     using G = ConvGeo<NT, NW, false, true>;
     asm volatile("" : "+v"(lane));
@@ -157,14 +145,14 @@ __device__ __forceinline__ void conv_dma_plane(const ConvArgs& a, const ConvRsrc
             const bool in = (unsigned)(iy0 + 2 * pr) < (unsigned)a.Hi && (unsigned)(ix0 + 2 * pc) < (unsigned)a.Wi && q < G::PH * PW;
             int off = (sbase + 2 * (pr * a.Wi + pc) * CIN + 8 * slot) * (int)sizeof(T);
             asm volatile("" : "+v"(off));
-            conv_lds_dma(xs, dst + piece * 1024, in ? off : 0x7FFFFFF0, 0);
+            gf_lds_dma(xs, dst + piece * 1024, in ? off : 0x7FFFFFF0, 0);
         }
     }
 }
 
 // request the REMAINDER patch of a tile (channels 192 .. 199 of every halo pixel: 16 B per pixel, pixel q at q * 16): pieces of 64 pixels
 template <typename T, int CIN, int NT, int NW>
-__device__ __forceinline__ void conv_dma_patch_rem(const ConvArgs& a, const ConvRsrc& xs, char* smem, int n, int y0, int x0, int wave, int lane) {
+__device__ __forceinline__ void conv_dma_patch_rem(const ConvArgs& a, const GfRsrc& xs, char* smem, int n, int y0, int x0, int wave, int lane) {
     using G = ConvGeo<NT, NW, true>;
     asm volatile("" : "+v"(lane));
     char* dst = smem + G::R_OFF;
@@ -177,7 +165,7 @@ __device__ __forceinline__ void conv_dma_patch_rem(const ConvArgs& a, const Conv
             const int pr = q / PW, pc = q - pr * PW;
             const bool in = (unsigned)(y0 - 1 + pr) < (unsigned)a.Hi && (unsigned)(x0 - 1 + pc) < (unsigned)a.Wi && q < G::PH * PW;
             const int off = sbase + (pr * a.Wi + pc) * CIN;
-            conv_lds_dma(xs, dst + piece * 1024, in ? off * (int)sizeof(T) : 0x7FFFFFF0, 0);
+            gf_lds_dma(xs, dst + piece * 1024, in ? off * (int)sizeof(T) : 0x7FFFFFF0, 0);
         }
     }
 }
@@ -242,10 +230,10 @@ __global__ __launch_bounds__(NW * 64) void conv3x3_kernel(ConvArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lp = lane & 15, g4 = lane >> 4;                       // MFMA 16x16x32: row / column of the lane, its k group
-    const ConvRsrc ws = conv_rsrc(a.wstream, (unsigned)NBLK * G::WBLK);
-    const ConvRsrc xs = conv_rsrc(a.x, (unsigned)a.N * a.Hi * a.Wi * CIN * (unsigned)sizeof(T));
-    const ConvRsrc rres = conv_rsrc(a.res, (unsigned)a.N * a.H * a.W * COUT * (unsigned)sizeof(T));
-    const ConvRsrc rout = conv_rsrc(a.out, (unsigned)a.N * a.H * a.W * COUT * (unsigned)sizeof(T));
+    const GfRsrc ws = gf_rsrc(a.wstream, (unsigned)NBLK * G::WBLK);
+    const GfRsrc xs = gf_rsrc(a.x, (unsigned)a.N * a.Hi * a.Wi * CIN * (unsigned)sizeof(T));
+    const GfRsrc rres = gf_rsrc(a.res, (unsigned)a.N * a.H * a.W * COUT * (unsigned)sizeof(T));
+    const GfRsrc rout = gf_rsrc(a.out, (unsigned)a.N * a.H * a.W * COUT * (unsigned)sizeof(T));
     typedef unsigned v4u __attribute__((ext_vector_type(4)));
     float* shiftv = reinterpret_cast<float*>(smem + G::SHIFT_OFF);
     for (int i = tid; i < COUT; i += NW * 64) shiftv[i] = a.shift ? a.shift[i] : 0.f;

@@ -106,19 +106,8 @@ __device__ __forceinline__ float fl_rnd(float x) { return gf_to_float(gf_from_fl
 __device__ __forceinline__ v16f fl_zero() { return v16f{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}; }
 
 // the weight ring: block g (counted over the whole kernel) sits in slot g & 1 and holds stream block g % NBLK
-struct FlRsrc {
-    __amdgpu_buffer_rsrc_t r;
-};
-__device__ __forceinline__ FlRsrc fl_rsrc(const void* p, unsigned bytes) {
-    return FlRsrc{__builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000)};
-}
-// LDS-DMA as buffer_load_dwordx4 ... lds (MUBUF): behind the FLAT form (global_load_lds) the compiler turns every LDS counter
-// wait into lgkmcnt(0) while a request is pending - which is always, here (see k9_encoder_fused.hip); scalar descriptor, 32-bit offsets
-__device__ __forceinline__ void fl_lds_dma(const FlRsrc& rs, char* dst, int voffset, int soffset) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs.r, (__attribute__((address_space(3))) void*)dst, 16, voffset, soffset, 0, 0);
-}
 struct FlRing {
-    FlRsrc ws;
+    GfRsrc ws;
     char* smem;
     int wave, lane;
     int blk;        // block being consumed (global count)
@@ -129,7 +118,7 @@ struct FlRing {
 __device__ __forceinline__ void fl_dma_block(const FlRing& r, int g, int sb) {
     char* dst = r.smem + W_OFF + (g & 1) * WBLK + r.wave * 4 * FRAG;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) fl_lds_dma(r.ws, dst + i * FRAG, r.lane * 16, sb * WBLK + (r.wave * 4 + i) * FRAG);
+    for (int i = 0; i < 4; ++i) gf_lds_dma(r.ws, dst + i * FRAG, r.lane * 16, sb * WBLK + (r.wave * 4 + i) * FRAG);
     __builtin_amdgcn_sched_barrier(0);
 }
 template <typename Frag>
@@ -164,12 +153,12 @@ __device__ __forceinline__ void fl_fetch_next(FlRing& r, Frag (&nx)[4], int st) 
 // window tile <- global rows by LDS-DMA: instruction i covers plane i >> 2, rows 8 (i & 3) .. + 7; the chunk swizzle of
 // gf_lds_off sits on the SOURCE side (the LDS image of a DMA is lane-linear).  Rows >= Lw re-read row Lw - 1 (finite values;
 // they only feed token slots that are masked or never stored).
-__device__ __forceinline__ void fl_tile_dma(const FlRsrc& wins, int win_byte_offset, int Lw, char* tile, int lane) {
+__device__ __forceinline__ void fl_tile_dma(const GfRsrc& wins, int win_byte_offset, int Lw, char* tile, int lane) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         const int row = 8 * (i & 3) + (lane >> 3), slot = lane & 7, c = slot ^ ((row >> 1) & 7);
         const int r = row < Lw ? row : Lw - 1;
-        fl_lds_dma(wins, tile + i * FRAG, r * (FC * 2) + (i >> 2) * 128 + c * 16, win_byte_offset);
+        gf_lds_dma(wins, tile + i * FRAG, r * (FC * 2) + (i >> 2) * 128 + c * 16, win_byte_offset);
     }
 }
 
@@ -185,8 +174,8 @@ __global__ __launch_bounds__(64 * FW, 2) void fine_layer(FlArgs a) {
     if (wave >= 4) __builtin_amdgcn_s_setprio(1);
 #endif
     const int my_groups = (a.groups - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
-    FlRing ring{fl_rsrc(a.wstream, (unsigned)NBLK * WBLK), smem, wave, lane, 0, 0, my_groups * NBLK};
-    const FlRsrc xrs = fl_rsrc(a.x, (unsigned)a.Nw * a.Lw * (FC * 2)), srs = fl_rsrc(a.src, (unsigned)a.Nw * a.Lw * (FC * 2));
+    FlRing ring{gf_rsrc(a.wstream, (unsigned)NBLK * WBLK), smem, wave, lane, 0, 0, my_groups * NBLK};
+    const GfRsrc xrs = gf_rsrc(a.x, (unsigned)a.Nw * a.Lw * (FC * 2)), srs = gf_rsrc(a.src, (unsigned)a.Nw * a.Lw * (FC * 2));
     fl_dma_block(ring, 0, 0);
     fl_dma_block(ring, 1, 1);
     for (int i = tid; i < 4 * FC; i += 64 * FW) vec[i] = a.ln[i];       // 4 x 128 floats

@@ -48,16 +48,6 @@ __device__ long long k12_trace[256 * 8 * 8];
 #define K12_T(i)
 #endif
 
-struct LatRsrc {
-    __amdgpu_buffer_rsrc_t r;
-};
-__device__ __forceinline__ LatRsrc lat_rsrc(const void* p, unsigned bytes) {
-    return LatRsrc{__builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000)};
-}
-__device__ __forceinline__ void lat_lds_dma(const LatRsrc& rs, char* dst, int voffset, int soffset) {      // 64 lanes x 16 B -> 1 KiB at dst
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs.r, (__attribute__((address_space(3))) void*)dst, 16, voffset, soffset, 0, 0);
-}
-
 template <typename T, int CIN, int COUT>
 __global__ __launch_bounds__(L12_NW * 64) void lateral_kernel(LatArgs a) {
     using Mm = Mma16<T>;
@@ -71,10 +61,10 @@ __global__ __launch_bounds__(L12_NW * 64) void lateral_kernel(LatArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lp = lane & 15, g4 = lane >> 4, odd = lane & 1;
-    const LatRsrc xs = lat_rsrc(a.x, (unsigned)a.P * CIN * (unsigned)sizeof(T));
-    const LatRsrc wsr = lat_rsrc(a.wfrag, (unsigned)W_BYTES);
-    const LatRsrc los = lat_rsrc(a.lo, (unsigned)a.N * a.h * a.w * COUT * (unsigned)sizeof(T));
-    const LatRsrc outs = lat_rsrc(a.out, (unsigned)a.P * COUT * (unsigned)sizeof(T));
+    const GfRsrc xs = gf_rsrc(a.x, (unsigned)a.P * CIN * (unsigned)sizeof(T));
+    const GfRsrc wsr = gf_rsrc(a.wfrag, (unsigned)W_BYTES);
+    const GfRsrc los = gf_rsrc(a.lo, (unsigned)a.N * a.h * a.w * COUT * (unsigned)sizeof(T));
+    const GfRsrc outs = gf_rsrc(a.out, (unsigned)a.P * COUT * (unsigned)sizeof(T));
 
     // XCD-aware walk (workgroups are dealt to the 8 XCDs round-robin): XCD x owns a contiguous range of tiles, so the rows of the
     // coarser map a run of tiles shares meet in one L2
@@ -95,13 +85,13 @@ __global__ __launch_bounds__(L12_NW * 64) void lateral_kernel(LatArgs a) {
         const int off = ((t * L12_TP + wave * 16 + q) * CIN + 8 * slot) * (int)sizeof(T);
         char* dst = smem + X_OFF + (buf * L12_NW + wave) * XW;
 #pragma unroll
-        for (int kc = 0; kc < KC; ++kc) lat_lds_dma(xs, dst + kc * 1024, off, kc * 64);
+        for (int kc = 0; kc < KC; ++kc) gf_lds_dma(xs, dst + kc * 1024, off, kc * 64);
     };
     // prologue: the weights (once per workgroup), the first tile
 #pragma unroll
     for (int i = 0; i < (KC * NCT + L12_NW - 1) / L12_NW; ++i) {
         const int f = wave + L12_NW * i;
-        if (f < KC * NCT) lat_lds_dma(wsr, smem + f * 1024, lane * 16, f * 1024);
+        if (f < KC * NCT) gf_lds_dma(wsr, smem + f * 1024, lane * 16, f * 1024);
     }
     dma_x(tile0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -285,10 +275,10 @@ __global__ __launch_bounds__(L12_NW * 64) void lateral_staged_kernel(LatArgs a) 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lp = lane & 15, g4 = lane >> 4, odd = lane & 1;
-    const LatRsrc xs = lat_rsrc(a.x, (unsigned)a.P * CIN * (unsigned)sizeof(T));
-    const LatRsrc wsr = lat_rsrc(a.wfrag, (unsigned)W_BYTES);
-    const LatRsrc los = lat_rsrc(a.lo, (unsigned)a.N * a.h * a.w * COUT * (unsigned)sizeof(T));
-    const LatRsrc outs = lat_rsrc(a.out, (unsigned)a.P * COUT * (unsigned)sizeof(T));
+    const GfRsrc xs = gf_rsrc(a.x, (unsigned)a.P * CIN * (unsigned)sizeof(T));
+    const GfRsrc wsr = gf_rsrc(a.wfrag, (unsigned)W_BYTES);
+    const GfRsrc los = gf_rsrc(a.lo, (unsigned)a.N * a.h * a.w * COUT * (unsigned)sizeof(T));
+    const GfRsrc outs = gf_rsrc(a.out, (unsigned)a.P * COUT * (unsigned)sizeof(T));
     const int nx8 = gridDim.x >= 8 ? 8 : 1;
     const int xcd = nx8 == 8 ? (int)(blockIdx.x & 7) : 0, xslot = nx8 == 8 ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;
     const int xper = nx8 == 8 ? (int)((gridDim.x + 7 - xcd) >> 3) : (int)gridDim.x;
@@ -304,7 +294,7 @@ __global__ __launch_bounds__(L12_NW * 64) void lateral_staged_kernel(LatArgs a) 
         const int q = l >> 2, slot = (l & 3) ^ ((q >> 1) & 3);
         const int off = ((t * L12_TP + wave * 16 + q) * CIN + 8 * slot) * (int)sizeof(T);
 #pragma unroll
-        for (int kc = 0; kc < KC; ++kc) lat_lds_dma(xs, wv + kc * 1024, off, kc * 64);
+        for (int kc = 0; kc < KC; ++kc) gf_lds_dma(xs, wv + kc * 1024, off, kc * 64);
     };
     // ---- per-tile state.  Wave-uniform: the row of the wave's 16 pixels (image n, row y), its two rows y0 / y1 of the coarser map and
     // xl0, the first staged column.  Per lane: LDS offsets of the four taps of its A / B / lone pieces, their weights, the store offsets.
@@ -331,7 +321,7 @@ __global__ __launch_bounds__(L12_NW * 64) void lateral_staged_kernel(LatArgs a) 
                 // (the last piece of a row is partial: its lanes behind the row's end are masked off - an out-of-range lane would write
                 // zeros over the start of the next row's area)
                 const int b = i * 1024 + l * 16;
-                if (b < LOROW) lat_lds_dma(los, wv + XW + r * LOROW + i * 1024, p0 < a.P ? rbase + b : 0x7FFFFFF0, 0);
+                if (b < LOROW) gf_lds_dma(los, wv + XW + r * LOROW + i * 1024, p0 < a.P ? rbase + b : 0x7FFFFFF0, 0);
             }
         }
         int el = lane;
@@ -415,7 +405,7 @@ __global__ __launch_bounds__(L12_NW * 64) void lateral_staged_kernel(LatArgs a) 
 #pragma unroll
     for (int i = 0; i < (KC * NCT + L12_NW - 1) / L12_NW; ++i) {
         const int f = wave + L12_NW * i;
-        if (f < KC * NCT) lat_lds_dma(wsr, smem + f * 1024, lane * 16, f * 1024);
+        if (f < KC * NCT) gf_lds_dma(wsr, smem + f * 1024, lane * 16, f * 1024);
     }
     dma_x(tile0);
     stage(tile0);

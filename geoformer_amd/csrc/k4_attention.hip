@@ -136,18 +136,6 @@ __device__ __forceinline__ typename Mma32<T>::Frag k4_vtr_frag(const char* img, 
     return __builtin_bit_cast(typename Mma32<T>::Frag, both);
 }
 
-// LDS-DMA (16-bit modes): 64 lanes x 16 B of a staged tile straight from the compact K / V^T buffers into LDS, no registers.
-// MUBUF form: the waits the compiler inserts stay counted (the FLAT form makes every LDS wait lgkmcnt(0)).
-struct AtRsrc {
-    __amdgpu_buffer_rsrc_t r;
-};
-__device__ __forceinline__ AtRsrc at_rsrc(const void* p, unsigned bytes) {
-    return AtRsrc{__builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000)};
-}
-__device__ __forceinline__ void at_lds_dma(const AtRsrc& rs, char* dst, int voffset, int soffset) {        // -> 1 KiB at dst
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs.r, (__attribute__((address_space(3))) void*)dst, 16, voffset, soffset, 0, 0);
-}
-
 // max(x[lane], x[lane ^ 32]) in every lane: one v_permlane32_swap (VALU) instead of a ds_bpermute, whose lgkmcnt(0) wait also
 // drained the fragment reads in flight
 __device__ __forceinline__ float half_max(float x) {
@@ -456,10 +444,10 @@ __global__ __launch_bounds__(256, QB <= 2 ? 2 : 1) void attn_self(AtArgs a) {
         // (round 3, with the tile passing through registers and two barriers: 335 us per 16-image call at 1195 keys, 218 us
         // with the staging compiled out)
         const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-        const AtRsrc rk = DIRECT ? at_rsrc((const T*)a.kmap + (size_t)n * a.L * a.ldk, (unsigned)((size_t)a.L * a.ldk * sizeof(T)))
-                                 : at_rsrc(kc, (unsigned)((size_t)a.Kpad * CC * sizeof(T)));
-        const AtRsrc rv = DIRECT ? at_rsrc((const T*)a.vmap + (size_t)n * a.L * a.ldv, (unsigned)((size_t)a.L * a.ldv * sizeof(T)))
-                                 : at_rsrc((const T*)a.vc + (size_t)n * CC * a.Kpad, (unsigned)((size_t)CC * a.Kpad * sizeof(T)));
+        const GfRsrc rk = DIRECT ? gf_rsrc((const T*)a.kmap + (size_t)n * a.L * a.ldk, (unsigned)((size_t)a.L * a.ldk * sizeof(T)))
+                                 : gf_rsrc(kc, (unsigned)((size_t)a.Kpad * CC * sizeof(T)));
+        const GfRsrc rv = DIRECT ? gf_rsrc((const T*)a.vmap + (size_t)n * a.L * a.ldv, (unsigned)((size_t)a.L * a.ldv * sizeof(T)))
+                                 : gf_rsrc((const T*)a.vc + (size_t)n * CC * a.Kpad, (unsigned)((size_t)CC * a.Kpad * sizeof(T)));
         // K image: 1 KiB group g = key rows 2g, 2g+1; slot s of row r holds chunk s ^ (r & 15) (k_off)
         // V^T image: group g = channels 16g..16g+15, 4 slots of 16 B; slot s of channel c holds chunk s ^ ((c >> 2) & 3) (vt_off)
         // (DIRECT: the V image is row-major like K's: group g = key rows 2g, 2g+1, slot s of row r holds chunk k4_vslot_chunk(r, s))
@@ -496,18 +484,18 @@ __global__ __launch_bounds__(256, QB <= 2 ? 2 : 1) void attn_self(AtArgs a) {
                 for (int i = 0; i < PW; ++i) {
                     // a key slot behind the count: an offset outside the map = an out-of-range lane: zeros in LDS
                     const int kofs = tokn[i] >= 0 ? tokn[i] * (int)(a.ldk * sizeof(T)) + kvo[i] : 0x7FFFFFF0;
-                    at_lds_dma(rk, img + (wv * PW + i) * 1024, kofs, 0);
+                    gf_lds_dma(rk, img + (wv * PW + i) * 1024, kofs, 0);
                 }
 #pragma unroll
                 for (int i = 0; i < PW; ++i) {
                     const int vofs = tokn[i] >= 0 ? tokn[i] * (int)(a.ldv * sizeof(T)) + vvo[i] : 0x7FFFFFF0;
-                    at_lds_dma(rv, img + KBYTES + (wv * PW + i) * 1024, vofs, 0);
+                    gf_lds_dma(rv, img + KBYTES + (wv * PW + i) * 1024, vofs, 0);
                 }
             } else {
 #pragma unroll
-                for (int i = 0; i < PW; ++i) at_lds_dma(rk, img + (wv * PW + i) * 1024, kvo[i], tile * KBYTES);
+                for (int i = 0; i < PW; ++i) gf_lds_dma(rk, img + (wv * PW + i) * 1024, kvo[i], tile * KBYTES);
 #pragma unroll
-                for (int i = 0; i < PW; ++i) at_lds_dma(rv, img + KBYTES + (wv * PW + i) * 1024, vvo[i], tile * (KT * (int)sizeof(T)));
+                for (int i = 0; i < PW; ++i) gf_lds_dma(rv, img + KBYTES + (wv * PW + i) * 1024, vvo[i], tile * (KT * (int)sizeof(T)));
             }
         };
         if constexpr (NB == 2) {

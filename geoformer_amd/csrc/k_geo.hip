@@ -474,15 +474,6 @@ struct CtArgs {
     int N, L, S, hq, wq, wk, tiles_x;
     float scale2;           // log2(e) / sqrt(D)
 };
-struct CtRsrc {
-    __amdgpu_buffer_rsrc_t r;
-};
-__device__ __forceinline__ CtRsrc ct_rsrc(const void* p, unsigned bytes) {
-    return CtRsrc{__builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000)};
-}
-__device__ __forceinline__ void ct_lds_dma(const CtRsrc& rs, char* dst, int voffset) {        // 64 lanes x 16 B -> 1 KiB at dst
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs.r, (__attribute__((address_space(3))) void*)dst, 16, voffset, 0, 0, 0);
-}
 typedef _Float16 ct_v2h __attribute__((ext_vector_type(2)));
 typedef gf_bf16 ct_v2b __attribute__((ext_vector_type(2)));
 typedef unsigned ct_u4 __attribute__((ext_vector_type(4)));
@@ -675,8 +666,8 @@ __global__ __launch_bounds__(256, CT_WAVES) void window_cross_tiled(CtArgs a) {
     const char* vimg = (const char*)a.vmap + (size_t)n * a.S * a.ldv * sizeof(T);
     if (tiled) {
         // 8 cells (x 128 bytes of this head) per request: lane -> (cell = 8 g + lane / 8, 16-byte piece = lane % 8)
-        const CtRsrc rk = ct_rsrc(kimg, (unsigned)((size_t)a.S * a.ldk * sizeof(T)));
-        const CtRsrc rv = ct_rsrc(vimg, (unsigned)((size_t)a.S * a.ldv * sizeof(T)));
+        const GfRsrc rk = gf_rsrc(kimg, (unsigned)((size_t)a.S * a.ldk * sizeof(T)));
+        const GfRsrc rv = gf_rsrc(vimg, (unsigned)((size_t)a.S * a.ldv * sizeof(T)));
         const int ncell = bh * bw, groups = (ncell + 7) >> 3;
         const float rbw = 1.0f / (float)bw;
         for (int g = wave; g < groups; g += 4) {
@@ -684,8 +675,8 @@ __global__ __launch_bounds__(256, CT_WAVES) void window_cross_tiled(CtArgs a) {
             const int by = (int)(((float)c + 0.5f) * rbw);    // exact for c, bw <= CT_CAP
             const int cellg = (y0 + by) * a.wk + x0 + (c - by * bw);
             const unsigned piece = (unsigned)head * 128u + (unsigned)(lane & 7) * 16u;
-            ct_lds_dma(rk, sK + g * 1024, (int)((unsigned)cellg * (unsigned)(a.ldk * sizeof(T)) + piece));
-            ct_lds_dma(rv, sV + g * 1024, (int)((unsigned)cellg * (unsigned)(a.ldv * sizeof(T)) + piece));
+            gf_lds_dma(rk, sK + g * 1024, (int)((unsigned)cellg * (unsigned)(a.ldk * sizeof(T)) + piece));
+            gf_lds_dma(rv, sV + g * 1024, (int)((unsigned)cellg * (unsigned)(a.ldv * sizeof(T)) + piece));
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }

@@ -2,7 +2,7 @@
 algorithm picks for the bench / eval shapes on gfx950 (`geoformer_amd/miopen_db/*.udb.txt, *.ufdb.txt`), so
 MIOpen's immediate mode picks them without a multi-minute search.  Round 6: the find-db also holds the problems of the fp32 parity leg
 and of the two training steps (forward, backward-data and backward-weights of the backbone's convolutions at 640x480x4 and 640x640x8:
-without them the FIRST training step of a process spent ~160 s inside MIOpen - `tools/r06_miopen_db2.sh` is the run that found them),
+without them the FIRST training step of a process spent ~160 s inside MIOpen - two whole `bench.py` runs against a user db found them),
 and MIOpen's compiled-kernel cache of those picks (`miopen_db/cache/*.ukdb`, a build artefact: git-ignored, it travels with the working
 tree like the built .so; without it the first use of a pick compiles its kernel).
 

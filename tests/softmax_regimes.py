@@ -4,7 +4,7 @@
 K4 (k4_attention.hip, 16-bit modes): a query's softmax reference m moves only when a 32-key tile's maximum exceeds it by more than
 K4_DEFER = 8 log2 units (and in the first tile).  Logits here are in those units: x = q' . k with the prescaled, rounded query
 q' = round_T(fp32(q) * fp32(log2(e) / 8)), exactly the operand the kernel multiplies.
-K1 (k1_stats_panel, k1_dual_softmax.hip): one lazily moved reference per row slot of a lane, LAZY = 64 log2 units; a lane rescales
+K1 (k1_stats_panel, k1_stats_panel.hip): one lazily moved reference per row slot of a lane, LAZY = 64 log2 units; a lane rescales
 when a tile's maximum passes its smallest reference by more than 64, and a tile is 'deep' when some column's maximum lies more than 64
 below kappa, the lane's largest reference.
 

@@ -1,5 +1,5 @@
 """K1 (gf_dual_softmax_match) at the bench shape, per kernel tag via the library's HIP-event profile:
-python tools/k1_time.py [pairs=8] [thr=0.0]     (GF_K1_CONF=panel selects the unpipelined pass-B form)"""
+python tools/k1_time.py [pairs=8] [thr=0.0]"""
 import ctypes, sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

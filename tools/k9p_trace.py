@@ -1,5 +1,5 @@
-"""Phase timeline of the wave-pair encoder kernel (needs a -DK9P_TRACE=1 build: tools/variant.sh k9p_trace k9_encoder_fused.hip -DK9P_TRACE=1,
-run with GF_LIB_PATH=tools/ab/k9p_trace.so).  Prints median s_memtime offsets (shader cycles) of the phase boundaries."""
+"""Phase timeline of the wave-pair encoder kernel (needs a -DK9P_TRACE=1 build: HIPCC_EXTRA=-DK9P_TRACE=1 python -m geoformer_amd.build;
+GF_LIB_PATH=<that .so> selects a library kept elsewhere).  Prints median s_memtime offsets (shader cycles) of the phase boundaries."""
 import sys, os, ctypes
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -1,5 +1,5 @@
 """The linear layers' weight gradient (k_train.hip: wgrad_kernel + wgrad_reduce) at the training step's shapes; run once per variant library
-(GF_LIB_PATH=tools/ab/wg384.so ...) to compare chunk targets.   python tools/wgrad_chunks_time.py"""
+(GF_LIB_PATH=<that .so> selects a library kept elsewhere) to compare chunk targets.   python tools/wgrad_chunks_time.py"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
