@@ -56,12 +56,33 @@ __global__ __launch_bounds__(256) void fine_gather(FgArgs a) {
     for (int c = t; c < a.CC; c += blockDim.x) co[c] = cf[c];
 }
 
-// The 16-bit inference form (channels-last fine maps, window tensor in the same type): ONE WAVE per (match, side) moves the
+// One 16-byte piece of 8 elements TF -> T in registers (TF == T: the piece itself); see fine_gather_rows below.
+template <typename TF, typename T>
+__device__ __forceinline__ v4u fg_convert8(v4u v) {
+    if constexpr (std::is_same<TF, T>::value) {
+        return v;
+    } else {
+        const gf_vec<TF, 8> x = __builtin_bit_cast(gf_vec<TF, 8>, v);
+        gf_vec<T, 8> o;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) o[k] = gf_from_float<T>(gf_to_float(x[k]));
+        return __builtin_bit_cast(v4u, o);
+    }
+}
+
+// The 16-bit inference form (channels-last 16-bit fine maps, 16-bit window tensor): ONE WAVE per (match, side) moves the
 // 25 x C window as 16-byte pieces - C / 8 lanes per window position, 64 / (C / 8) positions per instruction - and the coarse
 // feature row behind it; out-of-image positions are zeros (F.unfold's padding).  The general kernel above moves 2 bytes per
 // lane and instruction with half its threads idle (226 us per 8-pair call at the nominal load against ~100 us of HBM time).
-template <typename T>
+// TF == T: a plain copy.  TF != T (bf16 maps -> fp16 windows: the bf16-backbone / fp16-matching mode; or the reverse): the 8
+// elements of a piece are converted in registers between the load and the store - widened to fp32 (exact for both types), then
+// rounded ONCE to nearest even into T, the bits of torch's x.float().to(T) for every input pattern.  No clamp and no flush: a finite
+// bf16 value above 65504 becomes +-inf in fp16, one below fp16's subnormal spacing rounds to nearest even (to a subnormal or to
+// a signed zero).  The fp16 mode has the same range through its own backbone.  Same bytes per match as the copy: 16-byte loads
+// and stores either way.  The coarse row is in T already and stays a copy.
+template <typename TF, typename T>
 __global__ __launch_bounds__(256) void fine_gather_rows(FgArgs a) {
+    static_assert(sizeof(TF) == 2 && sizeof(T) == 2, "16-byte pieces of 8 elements on both sides");
     const int lane = threadIdx.x & 63, u = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (u >= 2 * a.M) return;
     const int side = u >= a.M, m = side ? u - a.M : u;
@@ -69,7 +90,7 @@ __global__ __launch_bounds__(256) void fine_gather_rows(FgArgs a) {
     const int cell = (int)(side ? a.j_ids[m] : a.i_ids[m]);
     const int wc = side ? a.w1c : a.w0c;
     const int Hf = side ? a.H1 : a.H0, Wf = side ? a.W1 : a.W0;
-    const T* f = (const T*)(side ? a.f1 : a.f0);
+    const TF* f = (const TF*)(side ? a.f1 : a.f0);
     const long sn = side ? a.s1n : a.s0n, sh = side ? a.s1h : a.s0h, sw = side ? a.s1w : a.s0w;
     const int cy = (cell / wc) * a.stride - a.W / 2, cx = (cell % wc) * a.stride - a.W / 2;
     const int ppp = a.C / 8, pieces = a.W * a.W * ppp;                  // 16-byte pieces per position / per window
@@ -78,7 +99,7 @@ __global__ __launch_bounds__(256) void fine_gather_rows(FgArgs a) {
     for (int e = lane; e < pieces; e += 64) {
         const int k = e / ppp, c8 = (e - k * ppp) * 8, y = cy + k / a.W, x = cx + k % a.W;
         v4u v = zero;
-        if (y >= 0 && y < Hf && x >= 0 && x < Wf) v = *reinterpret_cast<const v4u*>(f + b * sn + y * sh + x * sw + c8);
+        if (y >= 0 && y < Hf && x >= 0 && x < Wf) v = fg_convert8<TF, T>(*reinterpret_cast<const v4u*>(f + b * sn + y * sh + x * sw + c8));
         *reinterpret_cast<v4u*>(out + (size_t)k * a.C + c8) = v;
     }
     const T* cf = (const T*)(side ? a.c1 : a.c0) + ((size_t)b * (side ? a.S : a.L) + cell) * a.CC;
@@ -313,12 +334,12 @@ __global__ __launch_bounds__(1024) void fine_compact(FmArgs a) {
 
 template <typename TF, typename T>
 int fg_launch(const FgArgs& a, hipStream_t st) {
-    if constexpr (std::is_same<TF, T>::value && sizeof(T) == 2) {
+    if constexpr (sizeof(TF) == 2 && sizeof(T) == 2) {
         const bool rows16 = a.s0c == 1 && a.s1c == 1 && a.C % 8 == 0 && a.CC % 8 == 0 && (uintptr_t)a.f0 % 16 == 0 && (uintptr_t)a.f1 % 16 == 0 &&
                             (uintptr_t)a.c0 % 16 == 0 && (uintptr_t)a.c1 % 16 == 0 && (uintptr_t)a.win % 16 == 0 && (uintptr_t)a.ccat % 16 == 0 &&
                             a.s0n % 8 == 0 && a.s0h % 8 == 0 && a.s0w % 8 == 0 && a.s1n % 8 == 0 && a.s1h % 8 == 0 && a.s1w % 8 == 0;
         if (rows16) {
-            fine_gather_rows<T><<<(2 * a.M + 3) / 4, 256, 0, st>>>(a);
+            fine_gather_rows<TF, T><<<(2 * a.M + 3) / 4, 256, 0, st>>>(a);
             GF_CHECK_LAUNCH();
             return GF_OK;
         }
@@ -326,6 +347,12 @@ int fg_launch(const FgArgs& a, hipStream_t st) {
     fine_gather<TF, T><<<dim3(a.M, 2), 256, 0, st>>>(a);
     GF_CHECK_LAUNCH();
     return GF_OK;
+}
+
+template <typename TF>
+int fg_launch_to(int dtype, const FgArgs& a, hipStream_t st) {
+    return dtype == GF_F32 ? fg_launch<TF, float>(a, st)
+                           : dtype == GF_F16 ? fg_launch<TF, _Float16>(a, st) : fg_launch<TF, gf_bf16>(a, st);
 }
 
 }   // namespace
@@ -339,16 +366,13 @@ extern "C" int gf_fine_gather(const void* feat_f0, const void* feat_f1, int feat
     GF_CHECK_ARG(M > 0, "M must be > 0 (the M == 0 early return of fine_preprocess.py:35-38 is the caller's)");
     GF_CHECK_ARG(C > 0 && C <= 256 && window > 0 && stride > 0 && w0c > 0 && w1c > 0, "bad sizes");
     GF_CHECK_ARG(feat_dtype >= GF_F32 && feat_dtype <= GF_BF16 && dtype >= GF_F32 && dtype <= GF_BF16, "bad dtype");
-    GF_CHECK_ARG(feat_dtype == GF_F32 || dtype == GF_F32 || feat_dtype == dtype, "fp16 <-> bf16 conversion is not built");
     FgArgs a{feat_f0, feat_f1, strides0[0], strides0[1], strides0[2], strides0[3], strides1[0], strides1[1], strides1[2],
              strides1[3], H0, W0, H1, W1, C, feat_c0, feat_c1, L, S, CC, b_ids, i_ids, j_ids, M, w0c, w1c, stride, window,
              win_out, ccat_out};
     hipStream_t st = (hipStream_t)stream;
-    if (feat_dtype == GF_F32)
-        return dtype == GF_F32 ? fg_launch<float, float>(a, st)
-                               : dtype == GF_F16 ? fg_launch<float, _Float16>(a, st) : fg_launch<float, gf_bf16>(a, st);
-    if (feat_dtype == GF_F16) return dtype == GF_F32 ? fg_launch<_Float16, float>(a, st) : fg_launch<_Float16, _Float16>(a, st);
-    return dtype == GF_F32 ? fg_launch<gf_bf16, float>(a, st) : fg_launch<gf_bf16, gf_bf16>(a, st);
+    if (feat_dtype == GF_F32) return fg_launch_to<float>(dtype, a, st);
+    if (feat_dtype == GF_F16) return fg_launch_to<_Float16>(dtype, a, st);
+    return fg_launch_to<gf_bf16>(dtype, a, st);
 }
 
 extern "C" size_t gf_fine_match_workspace_bytes(int M) {

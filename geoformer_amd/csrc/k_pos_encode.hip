@@ -2,6 +2,12 @@
 // model/loftr_src/loftr/utils/position_encoding.py:37-42, followed by the permute/reshape of
 // model/full_model.py:69-77).  The sin/cos table is built on the host exactly as the reference builds
 // its buffer (:22-35) and passed in as fp32 [H, W, C]; the kernel is a strided read + add + cast.
+//
+// Every input / output type pair is built, bf16 -> fp16 and fp16 -> bf16 included (the bf16-backbone / fp16-matching mode reads the
+// backbone's bf16 maps and writes fp16 tokens: no cast pass over the maps in between).  The arithmetic is the same for all nine:
+// input widened to fp32 (exact), + the fp32 table, ONE rounding to nearest even into the output type - the bits of torch's
+// (x.float() + pe).to(out).  No clamp and no flush: a sum above 65504 becomes +-inf in fp16, one below fp16's subnormal spacing rounds
+// to nearest even like every other.  The fp16 mode has the same range through its own backbone.
 #include "gf_common.h"
 
 namespace {
@@ -91,6 +97,12 @@ int pe_launch(const PeArgs& a, hipStream_t st) {
     return GF_OK;
 }
 
+template <typename TI>
+int pe_launch_to(int out_dtype, const PeArgs& a, hipStream_t st) {
+    return out_dtype == GF_F32 ? pe_launch<TI, float>(a, st)
+                               : out_dtype == GF_F16 ? pe_launch<TI, _Float16>(a, st) : pe_launch<TI, gf_bf16>(a, st);
+}
+
 }   // namespace
 
 extern "C" int gf_pos_encode(const void* x, int x_dtype, long sn, long sc, long sh, long sw, const float* pe,
@@ -98,12 +110,9 @@ extern "C" int gf_pos_encode(const void* x, int x_dtype, long sn, long sc, long 
     GF_CHECK_ARG(x && pe && out, "null pointer");
     GF_CHECK_ARG(N > 0 && C > 0 && H > 0 && W > 0, "empty problem");
     GF_CHECK_ARG(x_dtype >= GF_F32 && x_dtype <= GF_BF16 && out_dtype >= GF_F32 && out_dtype <= GF_BF16, "bad dtype");
-    GF_CHECK_ARG(x_dtype == GF_F32 || out_dtype == GF_F32 || x_dtype == out_dtype, "fp16 <-> bf16 conversion is not built");
     PeArgs a{x, sn, sc, sh, sw, pe, out, N, C, H, W};
     hipStream_t st = (hipStream_t)stream;
-    if (x_dtype == GF_F32)
-        return out_dtype == GF_F32 ? pe_launch<float, float>(a, st)
-                                   : out_dtype == GF_F16 ? pe_launch<float, _Float16>(a, st) : pe_launch<float, gf_bf16>(a, st);
-    if (x_dtype == GF_F16) return out_dtype == GF_F32 ? pe_launch<_Float16, float>(a, st) : pe_launch<_Float16, _Float16>(a, st);
-    return out_dtype == GF_F32 ? pe_launch<gf_bf16, float>(a, st) : pe_launch<gf_bf16, gf_bf16>(a, st);
+    if (x_dtype == GF_F32) return pe_launch_to<float>(out_dtype, a, st);
+    if (x_dtype == GF_F16) return pe_launch_to<_Float16>(out_dtype, a, st);
+    return pe_launch_to<gf_bf16>(out_dtype, a, st);
 }

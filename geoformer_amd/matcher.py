@@ -24,7 +24,7 @@ import torch
 
 from . import ops
 from .model.cvpr_ds_config import get_default_cfg
-from .model.full_model import GeoFormer
+from .model.full_model import PRECISIONS, GeoFormer
 from .model.geo_config import get_cfg_model
 
 
@@ -180,10 +180,11 @@ def load_gray_scale_tensor(im_path, device, imsize=None, dfactor=8, value_to_sca
 class GeoFormerMatcher:
     def __init__(self, imsize, match_threshold, no_match_upscale=False, ckpt=None, device='cuda', precision='fp32',
                  miopen_search=False, preprocess='host'):
-        """precision / miopen_search / preprocess are additions: 'fp16' is the fast mode; miopen_search=True lets MIOpen search its
-        convolution algorithms once per new image shape (seconds each, ~25 % faster backbone afterwards: 6.8 -> 5.2 ms
-        per 480x640 pair) - worth it when a dataset repeats a few shapes; preprocess='device' moves gray conversion, resize and
-        normalisation of the decoded images from numpy to one kernel per image (load_gray_scale_tensor), same bits."""
+        """precision / miopen_search / preprocess are additions: 'fp16' is the fast mode ('bf16', 'bf16_fp16': GeoFormer.set_precision);
+        miopen_search=True lets MIOpen search its convolution algorithms once per new image shape (seconds each, ~25 % faster
+        backbone afterwards: 6.8 -> 5.2 ms per 480x640 pair) - worth it when a dataset repeats a few shapes; preprocess='device'
+        moves gray conversion, resize and normalisation of the decoded images from numpy to one kernel per image
+        (load_gray_scale_tensor), same bits."""
         if preprocess not in PREPROCESS:
             raise ValueError(f'preprocess must be one of {PREPROCESS}, got {preprocess!r}')
         if preprocess == 'device' and torch.device(device).type != 'cuda':
@@ -345,7 +346,7 @@ def eval_hpatches(matcher, data_root, ransac_thres=3, thres=(1, 3, 5, 10), scale
 #   python -m geoformer_amd.matcher match im1 im2 [--ckpt saved_ckpt/geoformer.ckpt] [--out matches.npz] [--preprocess device]
 #   python -m geoformer_amd.matcher hpatches /path/to/hpatches-sequences-release [--ckpt ...] [--preprocess device]
 # ---------------------------------------------------------------------------------------------
-def main(argv=None):
+def build_parser():
     """Defaults follow the reference per sub-command: `match` = inference.py:107 (imsize 640, matches scaled back to the
     original images); `hpatches` = eval_configs/geoformer.yml:7-11 with eval_Hpatches.py:96-100 (imsize 480, match
     threshold 0.2, no_match_upscale True -> the ground-truth homography is moved into resized coordinates, RANSAC
@@ -368,13 +369,20 @@ def main(argv=None):
     for p in (m, h):
         p.add_argument('--ckpt', default=None)
         p.add_argument('--match-threshold', type=float, default=0.2)
-        p.add_argument('--precision', choices=('fp32', 'fp16', 'bf16'), default='fp16',
+        p.add_argument('--precision', choices=PRECISIONS, default='fp16',
                        help="fp16 / bf16 = the fast modes (16-bit storage, fp32 accumulation; bf16 = BASELINE configs[1]'s wording); "
-                            "fp32 = the reference's arithmetic")
+                            "bf16_fp16 = bf16 backbone, matching path in fp16 storage (the position-encoding and fine-window kernels "
+                            "convert the backbone's maps as they read them; 260-pair outcome protocol against the fp32 oracle: dAUC@3 = -3.4e-4 +- 4.6e-4, "
+                            "where fp16 has +3.4e-4 +- 4.4e-4 and bf16 -1.5e-3 +- 1.4e-3; profiles/mixed_precision_outcome_260.txt); fp32 = the reference's arithmetic")
         p.add_argument('--preprocess', choices=PREPROCESS, default='host',
                        help='where the decoded images are converted to gray, resized and normalised: numpy on the host, or one HIP kernel '
                             'per image on the device (bit-identical output)')
-    args = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None):
+    """`python -m geoformer_amd.matcher match|hpatches ...` (arguments: build_parser)."""
+    args = build_parser().parse_args(argv)
     world = int(os.environ.get('WORLD_SIZE', '1'))
     local = int(os.environ.get('LOCAL_RANK', '0'))
     if world > 1:

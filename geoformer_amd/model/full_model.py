@@ -20,7 +20,13 @@ from .geo_config import default_cfg
 from .modules import (CoarseMatching, FineMatching2, FinePreprocess, GeoModule, LocalFeatureTransformer,
                       PositionEncodingSine, materialize_matches)
 
-_PRECISIONS = {'fp32': torch.float32, 'fp16': torch.float16, 'bf16': torch.bfloat16}
+# mode name -> (compute dtype: everything from the position encoding on, backbone dtype: the backbone and its four feature maps).
+# 'bf16_fp16': BASELINE configs[1] / [3]'s "bf16 backbone + HIP match kernels" with the matching path in fp16 storage (11 significant
+# bits instead of bf16's 8) - gf_pos_encode and gf_fine_gather, the two kernels that read the backbone's maps, convert while they
+# move the data, so no cast pass over the maps is added
+_PRECISIONS = {'fp32': (torch.float32, torch.float32), 'fp16': (torch.float16, torch.float16),
+               'bf16': (torch.bfloat16, torch.bfloat16), 'bf16_fp16': (torch.float16, torch.bfloat16)}
+PRECISIONS = tuple(_PRECISIONS)   # the mode names, for interfaces that offer the choice (matcher's --precision)
 
 
 _CONCURRENT_BACKBONES = [True]    # unequal-shape pairs: the two backbone calls on two streams (False: one after the other, for A/B)
@@ -50,13 +56,14 @@ class GeoFormer(nn.Module):
         self.concurrent_backbones = True
         self.set_precision(geoformer_cfg.get('precision', 'fp32'))
 
-    # -- precision of the matching path: 'fp32' (parity mode), 'fp16' or 'bf16' (16-bit storage, fp32 accumulate)
+    # -- precision mode: 'fp32' (parity mode), 'fp16' or 'bf16' (16-bit storage, fp32 accumulate), 'bf16_fp16' (bf16 backbone, fp16
+    # matching path); backbone_dtype overrides the mode's backbone dtype
     def set_precision(self, precision: str, backbone_dtype: Optional[torch.dtype] = None):
         if precision not in _PRECISIONS:
-            raise ValueError(f"precision must be one of {sorted(_PRECISIONS)}")
+            raise ValueError(f"precision must be one of {sorted(_PRECISIONS)}, got {precision!r}")
         self.precision = precision
-        self.compute_dtype = _PRECISIONS[precision]
-        self.backbone_dtype = backbone_dtype or self.compute_dtype
+        self.compute_dtype, mode_backbone_dtype = _PRECISIONS[precision]
+        self.backbone_dtype = backbone_dtype or mode_backbone_dtype
         self.backbone.to(self.backbone_dtype)
         self._fused[0] = None
         self._drop_graphs()
@@ -76,7 +83,7 @@ class GeoFormer(nn.Module):
                 m.invalidate()
 
     def _inference_backbone(self):
-        """fp16 inference form of the backbone (BN folded, channels_last, MIOpen convolutions + HIP glue
+        """16-bit inference form of the backbone in `backbone_dtype` (BN folded, channels_last, MIOpen convolutions + HIP glue
         kernels; model/backbone.py FusedInferenceBackbone).  The fp32 parity mode keeps the unfused module
         (bit-for-bit the reference's op sequence)."""
         if self._fused[0] is None:
@@ -203,7 +210,9 @@ class GeoFormer(nn.Module):
 
     def forward_features(self, data, feat_c0, feat_f0, feat_c1, feat_f1, static_only=False):
         """Everything after the backbone.  Public so that parity tests and benchmarks can drive the
-        matching path with given feature maps ([N,256,h,w] coarse, [N,128,4h,4w] fine)."""
+        matching path with given feature maps ([N,256,h,w] coarse, [N,128,4h,4w] fine).  The maps keep their own dtype
+        (`backbone_dtype` when they come from the backbone): the two kernels that read them, gf_pos_encode (here and in
+        GeoModule.forward) and gf_fine_gather (FinePreprocess.forward), write `compute_dtype`; nothing else touches them."""
         dt = self.compute_dtype
         data.update({'hw0_c': torch.tensor(feat_c0.shape[2:]), 'hw1_c': torch.tensor(feat_c1.shape[2:]),
                      'hw0_f': torch.tensor(feat_f0.shape[2:]), 'hw1_f': torch.tensor(feat_f1.shape[2:])})

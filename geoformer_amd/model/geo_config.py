@@ -1,6 +1,7 @@
 """GeoFormer hyper-parameters: same keys and values as the reference's model/geo_config.py:10-17
 (lower-cased dict `default_cfg`), without the yacs dependency.  One optional key is added:
-'precision' ('fp32' = parity mode, 'fp16' = fp16 storage / fp32 accumulate); absent -> 'fp32'."""
+'precision' ('fp32' = parity mode, 'fp16' / 'bf16' = 16-bit storage / fp32 accumulate, 'bf16_fp16' = bf16 backbone with the
+matching path in fp16 storage); absent -> 'fp32'."""
 import copy
 
 _DEFAULT = {

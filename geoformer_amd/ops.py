@@ -140,7 +140,8 @@ def _i32p(t):
 
 
 def pos_encode(x, pe_hwc, out_dtype, out=None):
-    """a1.  x [N,C,H,W] (any strides, fp32/fp16), pe_hwc fp32 [H,W,C] on the device -> [N, H*W, C] (into `out` if given)."""
+    """a1.  x [N,C,H,W] (any strides; fp32, fp16 or bf16), pe_hwc fp32 [H,W,C] on the device -> [N, H*W, C] of out_dtype (into `out`
+    if given).  Any input / output dtype pair, bf16 -> fp16 and fp16 -> bf16 included: bit-equal to (x.float() + pe).to(out_dtype)."""
     _need_cuda(x, pe_hwc)
     N, C, H, W = x.shape
     if out is None:
@@ -480,8 +481,9 @@ def window_cross_attention_backward(q, kmap, vmap, dout, win, nhead=4):
 
 
 def fine_gather(feat_f0, feat_f1, feat_c0, feat_c1, b_ids, i_ids, j_ids, w0c, w1c, stride, window, out_dtype):
-    """K7.  feat_f* [N,Cf,H,W] any strides; feat_c* [N,L,CC] contiguous of out_dtype; ids int64 [M] (M > 0)
-    -> (win [2M, W*W, Cf], ccat [2M, CC])."""
+    """K7.  feat_f* [N,Cf,H,W] any strides, both of one dtype (fp32, fp16 or bf16; it need not be out_dtype); feat_c* [N,L,CC]
+    contiguous of out_dtype; ids int64 [M] (M > 0) -> (win [2M, W*W, Cf], ccat [2M, CC]), both of out_dtype.  The window values
+    are feat.float().to(out_dtype) bit for bit (bf16 maps -> fp16 windows: the 'bf16_fp16' mode; no clamp: beyond fp16's range -> inf)."""
     _need_cuda(feat_f0, feat_f1, feat_c0, feat_c1, b_ids)
     M = b_ids.shape[0]
     Cf = feat_f0.shape[1]

@@ -197,6 +197,9 @@ int gf_coarse_loss_backward(int N, int L, int S, int C, const uint8_t* mask0, co
  *          and the permute/reshape of model/full_model.py:69-77
  *   out[n, y*W+x, c] = x[n,c,y,x] + pe[y,x,c];  x viewed as [N,C,H,W] through element strides
  *   (NCHW or channels_last), pe fp32 [H,W,C] (host table built as position_encoding.py:22-35).
+ *   x_dtype and out_dtype are independent: every pair of GF_F32 / GF_F16 / GF_BF16 is built (bf16 maps -> fp16 tokens is the
+ *   'bf16_fp16' mode).  x is widened to fp32, the sum is rounded once to nearest even into out_dtype: the bits of torch's
+ *   (x.float() + pe).to(out).  No clamp, no flush: a sum beyond fp16's range becomes +-inf.
  * ------------------------------------------------------------------------------------------ */
 int gf_pos_encode(const void* x, int x_dtype, long sn, long sc, long sh, long sw, const float* pe,
                   void* out, int out_dtype, int N, int C, int H, int W, void* stream);
@@ -441,6 +444,11 @@ int gf_window_cross_attention_tiled(const void* q, const void* kmap, const void*
  * (model/loftr_src/loftr/loftr_module/fine_preprocess.py:41-61)
  *   feat_f0/1 viewed as [N,C,H,W] through strides (4 longs each); feat_c0 [N,L,CC], feat_c1 [N,S,CC];
  *   win_out [2M, W*W, C] (image0 windows then image1), ccat_out [2M, CC].
+ *   feat_dtype (the fine maps) and dtype (feat_c*, win_out, ccat_out) are independent: every pair of GF_F32 / GF_F16 / GF_BF16 is
+ *   built.  A window element is the map's value widened to fp32 and rounded once to nearest even into dtype (torch's
+ *   x.float().to(dtype) for every bit pattern; no clamp, no flush: a finite bf16 value above 65504 becomes +-inf in fp16).  Two
+ *   16-bit types with channels-last maps (C % 8 == 0, CC % 8 == 0, 16-byte aligned rows) take the one-wave-per-window kernel
+ *   with 16-byte loads and stores, converting in registers when the types differ.
  * ------------------------------------------------------------------------------------------ */
 int gf_fine_gather(const void* feat_f0, const void* feat_f1, int feat_dtype, const long* strides0,
                    const long* strides1, int H0, int W0, int H1, int W1, int C, const void* feat_c0,
