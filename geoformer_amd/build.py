@@ -6,6 +6,7 @@ recompiles only what changed.
 """
 import hashlib
 import os
+import shutil
 import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
@@ -16,6 +17,10 @@ OBJ = os.path.join(CSRC, '_obj')
 LIB = os.path.join(HERE, 'libgeoformer_hip.so')
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-value'] + os.environ.get('HIPCC_EXTRA', '').split()
+# the host C++ compiler; where none is on PATH, the clang that hipcc itself drives (same flags, no offload)
+HOST_CXX = os.environ.get('CXX') or shutil.which('c++') or shutil.which('g++') or '/opt/rocm/lib/llvm/bin/clang++'
+HOST_FLAGS = ['-O2', '-ffp-contract=off', '-std=c++17', '-fPIC']
+POSE_HOST_LIB = os.path.join(OBJ, 'libpose_host.so')
 
 
 def _headers_digest():
@@ -52,8 +57,28 @@ def _compile(src, hdig, verbose):
     return obj
 
 
+def build_pose_host(verbose=True):
+    """TEST INFRASTRUCTURE: the serial host form of the essential-matrix RANSAC (csrc/host/pose_host.cpp over csrc/pose_solver.h, the
+    text k_pose.hip compiles for the device), built by the host C++ compiler without offload.  Only tests load it."""
+    os.makedirs(OBJ, exist_ok=True)
+    src = os.path.join(CSRC, 'host', 'pose_host.cpp')
+    h = hashlib.sha256()
+    for f in (src, os.path.join(CSRC, 'pose_solver.h'), os.path.join(CSRC, 'gf_hash.h')):
+        h.update(open(f, 'rb').read())
+    h.update(' '.join([HOST_CXX, *HOST_FLAGS]).encode())
+    stamp_file = os.path.join(OBJ, 'pose_host.stamp')
+    if not (os.path.exists(POSE_HOST_LIB) and os.path.exists(stamp_file) and open(stamp_file).read() == h.hexdigest()):
+        cmd = [HOST_CXX, *HOST_FLAGS, '-shared', '-o', POSE_HOST_LIB, src]
+        if verbose:
+            print(' '.join(cmd), flush=True)
+        subprocess.run(cmd, check=True)
+        open(stamp_file, 'w').write(h.hexdigest())
+    return POSE_HOST_LIB
+
+
 def build(verbose=True, jobs=4):
     os.makedirs(OBJ, exist_ok=True)
+    build_pose_host(verbose)
     srcs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.hip'))
     hdig = _headers_digest()
     with ThreadPoolExecutor(jobs) as ex:

@@ -16,6 +16,7 @@
 #include <math.h>
 
 #include "gf_common.h"
+#include "gf_hash.h"                      // mix32 / draw: shared with k_pose.hip
 
 #pragma clang fp contract(off)
 
@@ -44,19 +45,6 @@ struct RsArgs {
     int32_t* valid;          // [N]
     uint8_t* keep;           // [cap] 1 = match feeds the inlier maps (inlier, or any match when no model)
 };
-
-__device__ __forceinline__ uint32_t mix32(uint32_t x) {
-    x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
-    return x;
-}
-__device__ __forceinline__ uint32_t draw(uint32_t seed, uint32_t sample, uint32_t t, uint32_t k, uint32_t attempt) {
-    uint32_t x = seed * 0x9E3779B1u;
-    x = mix32(x ^ (sample + 0x7F4A7C15u));
-    x = mix32(x ^ (t * 0x85EBCA6Bu + 0x165667B1u));
-    x = mix32(x ^ (k * 0xC2B2AE35u + 0x27D4EB2Fu));
-    x = mix32(x ^ (attempt * 0x9E3779B1u + 0x61C88647u));
-    return x;
-}
 
 __device__ int rs_solve(double* a, double* b, int n) {
     for (int c = 0; c < n; ++c) {

@@ -276,6 +276,21 @@ def estimate_homography(matches, thr, device='cuda'):
     return rs['M'][0].cpu().numpy(), rs['keep'][:len(m)].cpu().numpy().astype(bool)
 
 
+def estimate_relative_pose(matches, K0, K1, thr=0.5, device='cuda'):
+    """Essential-matrix RANSAC + pose recovery from [n,4] pixel matches on the device (estimate_pose of the reference's metrics.py);
+    returns (R, t, inlier mask) or None."""
+    if len(matches) < 5:
+        return None
+    m = torch.as_tensor(np.asarray(matches), dtype=torch.float32, device=device)
+    counts = torch.tensor([len(m), len(m)], dtype=torch.int32, device=device)
+    k0 = torch.as_tensor(np.asarray(K0), dtype=torch.float32, device=device).reshape(1, 3, 3)
+    k1 = torch.as_tensor(np.asarray(K1), dtype=torch.float32, device=device).reshape(1, 3, 3)
+    rs = ops.ransac_essential(m[:, :2].contiguous(), m[:, 2:4].contiguous(), counts, 1, k0, k1, pixel_thr=thr)
+    if int(rs['valid'][0]) == 0:
+        return None
+    return rs['R'][0].cpu().numpy(), rs['t'][0].cpu().numpy(), rs['inliers'].cpu().numpy().astype(bool)
+
+
 def corner_error(H_pred, H_gt, w, h):
     corners = np.array([[0, 0, 1], [0, h - 1, 1], [w - 1, 0, 1], [w - 1, h - 1, 1.0]])
     a = corners @ np.asarray(H_gt).T

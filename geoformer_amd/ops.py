@@ -333,6 +333,51 @@ def ransac_homography(mkpts0_c, mkpts1_c, counts, N, scale, scale0=None, scale1=
     return {'kp0': kp[0], 'kp1': kp[1], 'M': M, 'M_f32': Mf[0], 'Minv_f32': Mf[1], 'valid': valid, 'keep': keep}
 
 
+POSE_RANSAC_ITERS = 1024        # fixed, not adaptive (OpenCV's own cap is 1000); a positive multiple of 32
+
+
+def _intrinsics(K, N, dev):
+    return _contig(K.to(device=dev, dtype=torch.float32).reshape(N, 9))
+
+
+def ransac_essential(mkpts0, mkpts1, counts, N, K0, K1, pixel_thr=0.5, iters=POSE_RANSAC_ITERS, seed=RANSAC_SEED):
+    """Device essential-matrix RANSAC + pose recovery (metrics.py:72-98 without its cv2 host round trip).  mkpts0/mkpts1 fp32 [M,2] pixel
+    keypoints sorted by pair, counts int32 [1+N] on the device, K0/K1 [N,3,3].  Returns dict(E fp64 [N,3,3] of Frobenius norm 1,
+    R fp64 [N,3,3], t fp64 [N,3] unit, valid int32 [N], n_inliers int32 [N], inliers uint8 [M], hypothesis int32 [N,2])."""
+    _need_cuda(mkpts0, mkpts1, counts)
+    dev = mkpts0.device
+    cap = mkpts0.shape[0]
+    m0 = _contig(mkpts0.float()) if cap else torch.zeros(1, 2, dtype=torch.float32, device=dev)
+    m1 = _contig(mkpts1.float()) if cap else torch.zeros(1, 2, dtype=torch.float32, device=dev)
+    k0, k1 = _intrinsics(K0, N, dev), _intrinsics(K1, N, dev)
+    E = torch.empty(N, 3, 3, dtype=torch.float64, device=dev)
+    R = torch.empty(N, 3, 3, dtype=torch.float64, device=dev)
+    t = torch.empty(N, 3, dtype=torch.float64, device=dev)
+    valid = torch.empty(N, dtype=torch.int32, device=dev)
+    nin = torch.empty(N, dtype=torch.int32, device=dev)
+    best = torch.empty(N, 2, dtype=torch.int32, device=dev)
+    inl = torch.zeros(max(cap, 1), dtype=torch.uint8, device=dev)
+    L_ = _lib.lib()
+    ws = _ws.get('pose', L_.gf_pose_workspace_bytes(N, max(int(iters), 1)), dev)
+    check(L_.gf_pose_essential_ransac(_p(m0), _p(m1), _p(counts), N, max(cap, 1), _p(k0), _p(k1), float(pixel_thr), int(iters), int(seed),
+                                      _p(E), _p(R), _p(t), _p(valid), _p(nin), _p(best), _p(inl), _p(ws), ws.numel(), _stream()),
+          'gf_pose_essential_ransac')
+    return {'E': E, 'R': R, 't': t, 'valid': valid, 'n_inliers': nin, 'inliers': inl[:cap], 'hypothesis': best}
+
+
+def epipolar_errors(mkpts0, mkpts1, m_bids, T_0to1, K0, K1):
+    """Squared symmetric epipolar distance of every match under E = [t]x R of its pair's T_0to1 (metrics.py:30-69), fp32 [M]."""
+    _need_cuda(mkpts0, mkpts1, m_bids, T_0to1)
+    dev = mkpts0.device
+    M, N = mkpts0.shape[0], T_0to1.shape[0]
+    out = torch.empty(M, dtype=torch.float32, device=dev)
+    T = _contig(T_0to1.to(device=dev, dtype=torch.float32).reshape(N, 16))
+    check(_lib.lib().gf_epipolar_errors(_p(_contig(mkpts0.float())), _p(_contig(mkpts1.float())), _p(_contig(m_bids.to(torch.int64))), M, _p(T),
+                                        _p(_intrinsics(K0, N, dev)), _p(_intrinsics(K1, N, dev)), N, _p(out), _stream()),
+          'gf_epipolar_errors')
+    return out
+
+
 def window_geometry(H_f32, valid, grid_hw, img_hw, key_grid_w, scale=8, window_size=5, window_scale=None,
                     debug=False):
     """a8.  H_f32 [N,3,3] maps the query grid (grid_hw cells) into the image of size img_hw (pixels).

@@ -37,6 +37,10 @@ def main(argv=None):
                     help='with --global-batch-seed: the global batch is a base batch of (world x batch / dup) pairs repeated dup times')
     ap.add_argument('--lr', type=float, default=None, help='canonical lr override (check mode)')
     ap.add_argument('--no-clip', action='store_true', help='no gradient clipping (check mode)')
+    ap.add_argument('--validate', type=int, default=0, metavar='K',
+                    help='after training: K synthetic MegaDepth-style batches through the validation step (device essential-matrix RANSAC, '
+                         'epipolar errors) on RANK 0 ONLY - the other ranks wait, nothing is gathered - which prints auc@5/10/20 and '
+                         'prec@5e-04 over exactly those K batches')
     ap.add_argument('--report', default=None,
                     help='rank 0 writes a JSON report: per-step losses averaged over the ranks, whether the parameters of all ranks '
                          'are bit-identical after the last step, and a float64 checksum per parameter')
@@ -101,6 +105,18 @@ def main(argv=None):
             torch.save({'state_dict': step.model.state_dict()}, args.save)
     if args.report:
         write_report(args.report, step.model, losses, rank, world, ddp)
+    if args.validate > 0:
+        # rank 0 alone: an eval-mode forward runs no collective (SyncBatchNorm uses its running statistics), so the other ranks simply
+        # wait at the barrier and the printed numbers cover all K batches
+        if rank == 0:
+            from .trainer import synthetic_megadepth_batch
+            from .validate import ValidationStep
+            vstep = ValidationStep(step.model, step.cfg)
+            outs = [vstep(synthetic_megadepth_batch(args.batch, tuple(args.size), seed=7000 + k, device=dev)) for k in range(args.validate)]
+            agg = vstep.aggregate(outs)
+            print('validation: ' + ' '.join(f'{k} {float(v):.4f}' for k, v in agg.items()), flush=True)
+        if ddp:
+            torch.distributed.barrier()
     if ddp:
         torch.distributed.destroy_process_group()
     return float(loss)

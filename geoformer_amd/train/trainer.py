@@ -26,6 +26,9 @@ DEFAULT_TRAINER_CFG = {       # model/loftr_src/config/default.py:103-165 with t
     'warmup_type': 'linear', 'warmup_ratio': 0.1, 'warmup_step': 1875, 'scheduler': 'MultiStepLR',
     'scheduler_interval': 'epoch', 'mslr_milestones': [8, 12, 16, 20, 24], 'mslr_gamma': 0.5, 'cosa_tmax': 30,
     'elr_gamma': 0.999992, 'gradient_clipping': 0.5,
+    # validation (train/validate.py, train/metrics.py): TRAINER.EPI_ERR_THR / RANSAC_PIXEL_THR / RANSAC_CONF.  ransac_conf is accepted and
+    # UNUSED: the device RANSAC runs a fixed number of hypotheses (ops.POSE_RANSAC_ITERS), an adaptive stop would need a host decision
+    'epi_err_thr': 5e-4, 'ransac_pixel_thr': 0.5, 'ransac_conf': 0.99999,
 }
 
 

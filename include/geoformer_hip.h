@@ -356,6 +356,35 @@ int gf_ransac_homography_v2(const float* mkpts0_c, const float* mkpts1_c, const 
                             size_t workspace_bytes, void* stream, int lm_iters);
 
 /* ------------------------------------------------------------------------------------------
+ * relative pose on the device (validation metrics)
+ * replaces estimate_pose (model/loftr_src/utils/metrics.py:72-98: cv2.findEssentialMat(..., RANSAC) + cv2.recoverPose, one host
+ * round trip per pair) and symmetric_epipolar_distance / compute_symmetrical_epipolar_errors (:30-69).  OpenCV parity is
+ * unpinned; the algorithm is the one stated in geoformer_amd/csrc/pose_solver.h (five-point minimal solver, Sampson inliers,
+ * closed-form decomposition, cheirality vote over the inliers), which also compiles for the host: bit-exact against that build.
+ *   gf_pose_essential_ransac
+ *     mkpts0/mkpts1 [cap,2] fp32 pixel keypoints sorted by pair, counts int32[1+N] (total, then per pair) in DEVICE memory;
+ *     K0, K1 fp32 [N,9]; keypoints are normalised as (p - (K[0][2], K[1][2])) / (K[0][0], K[1][1]) (:76-77) and the threshold is
+ *     pixel_thr / mean(K0[0][0], K1[1][1], K0[0][0], K1[1][1]) (:80), both computed on the device;
+ *     iters: FIXED number of hypotheses per pair (no adaptive stop: that would need a host decision), a positive multiple of 32;
+ *     a hypothesis = 5 distinct matches drawn by the counter-based hash of gf_ransac_homography from (seed, pair, hypothesis);
+ *     outputs per pair: E fp64 [N,9] (Frobenius norm 1), R fp64 [N,9], t fp64 [N,3] (unit), valid int32 [N] (0 = the reference's
+ *     `ret is None`: fewer than 5 matches, no hypothesis with 5 inliers, or no candidate in front of both cameras), n_inliers
+ *     int32 [N], best int32 [N,2] (chosen hypothesis and root, -1 when invalid); inliers uint8 [cap] per match (all 0 for an
+ *     invalid pair; entries past the total count are not written).
+ *   gf_epipolar_errors
+ *     m_bids int64 [M] pair of every match, T_0to1 fp32 [N,16], E = [t]x R; epi_errs fp32 [M] = (x1^T E x0)^2 (1 / (Ex0[0]^2 +
+ *     Ex0[1]^2) + 1 / (E^Tx1[0]^2 + E^Tx1[1]^2)) on normalised coordinates, fp64 arithmetic rounded once (NaN for a pair id
+ *     outside [0, N)).
+ * ------------------------------------------------------------------------------------------ */
+size_t gf_pose_workspace_bytes(int N, int iters);
+int gf_pose_essential_ransac(const float* mkpts0, const float* mkpts1, const int32_t* counts, int N, int capacity,
+                             const float* K0, const float* K1, float pixel_thr, int iters, uint32_t seed, double* E,
+                             double* R, double* t, int32_t* valid, int32_t* n_inliers, int32_t* best, uint8_t* inliers,
+                             void* workspace, size_t workspace_bytes, void* stream);
+int gf_epipolar_errors(const float* mkpts0, const float* mkpts1, const int64_t* m_bids, int M, const float* T_0to1,
+                       const float* K0, const float* K1, int N, float* epi_errs, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * a8  window geometry
  * replaces get_map_keypoints (utils/common_utils.py:137-144) + warp_points_batch
  * (utils/homography.py:86-105) + generate_window (utils/common_utils.py:65-91) + the cell lookup of
