@@ -129,6 +129,8 @@ SIGNATURES = {
                               c_void_p, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                               c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     'gf_image_gray_resize': (c_int, [c_void_p, c_int, c_int, c_int, ctypes.c_longlong, c_void_p, c_int, c_int, c_int, c_void_p]),
+    'gf_image_warp_resize': (c_int, [c_void_p, c_int, c_int, c_int, ctypes.c_longlong, ctypes.POINTER(ctypes.c_double), c_int, c_int, c_void_p,
+                                     c_int, c_int, c_int, ctypes.POINTER(c_float), c_void_p]),
 }
 
 

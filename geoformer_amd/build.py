@@ -21,6 +21,7 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-val
 HOST_CXX = os.environ.get('CXX') or shutil.which('c++') or shutil.which('g++') or '/opt/rocm/lib/llvm/bin/clang++'
 HOST_FLAGS = ['-O2', '-ffp-contract=off', '-std=c++17', '-fPIC']
 POSE_HOST_LIB = os.path.join(OBJ, 'libpose_host.so')
+WARP_HOST_LIB = os.path.join(OBJ, 'libwarp_host.so')
 
 
 def _headers_digest():
@@ -57,28 +58,40 @@ def _compile(src, hdig, verbose):
     return obj
 
 
-def build_pose_host(verbose=True):
-    """TEST INFRASTRUCTURE: the serial host form of the essential-matrix RANSAC (csrc/host/pose_host.cpp over csrc/pose_solver.h, the
-    text k_pose.hip compiles for the device), built by the host C++ compiler without offload.  Only tests load it."""
+def _build_host_lib(lib, stamp_name, src, headers, verbose):
     os.makedirs(OBJ, exist_ok=True)
-    src = os.path.join(CSRC, 'host', 'pose_host.cpp')
     h = hashlib.sha256()
-    for f in (src, os.path.join(CSRC, 'pose_solver.h'), os.path.join(CSRC, 'gf_hash.h')):
+    for f in (src, *headers):
         h.update(open(f, 'rb').read())
     h.update(' '.join([HOST_CXX, *HOST_FLAGS]).encode())
-    stamp_file = os.path.join(OBJ, 'pose_host.stamp')
-    if not (os.path.exists(POSE_HOST_LIB) and os.path.exists(stamp_file) and open(stamp_file).read() == h.hexdigest()):
-        cmd = [HOST_CXX, *HOST_FLAGS, '-shared', '-o', POSE_HOST_LIB, src]
+    stamp_file = os.path.join(OBJ, stamp_name)
+    if not (os.path.exists(lib) and os.path.exists(stamp_file) and open(stamp_file).read() == h.hexdigest()):
+        cmd = [HOST_CXX, *HOST_FLAGS, '-shared', '-o', lib, src]
         if verbose:
             print(' '.join(cmd), flush=True)
         subprocess.run(cmd, check=True)
         open(stamp_file, 'w').write(h.hexdigest())
-    return POSE_HOST_LIB
+    return lib
+
+
+def build_pose_host(verbose=True):
+    """TEST INFRASTRUCTURE: the serial host form of the essential-matrix RANSAC (csrc/host/pose_host.cpp over csrc/pose_solver.h, the
+    text k_pose.hip compiles for the device), built by the host C++ compiler without offload.  Only tests load it."""
+    return _build_host_lib(POSE_HOST_LIB, 'pose_host.stamp', os.path.join(CSRC, 'host', 'pose_host.cpp'),
+                           (os.path.join(CSRC, 'pose_solver.h'), os.path.join(CSRC, 'gf_hash.h')), verbose)
+
+
+def build_warp_host(verbose=True):
+    """TEST INFRASTRUCTURE: the perspective warp and the brightness / contrast rule of the homography-pair generator on the host
+    (csrc/host/warp_host.cpp over csrc/warp_spec.h, the text k_homo_pair.hip compiles for the device).  Only tests load it."""
+    return _build_host_lib(WARP_HOST_LIB, 'warp_host.stamp', os.path.join(CSRC, 'host', 'warp_host.cpp'),
+                           (os.path.join(CSRC, 'warp_spec.h'),), verbose)
 
 
 def build(verbose=True, jobs=4):
     os.makedirs(OBJ, exist_ok=True)
     build_pose_host(verbose)
+    build_warp_host(verbose)
     srcs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.hip'))
     hdig = _headers_digest()
     with ThreadPoolExecutor(jobs) as ex:

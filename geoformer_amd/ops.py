@@ -183,6 +183,56 @@ def image_gray_resize(src_u8, wt, ht, out=None, normalised=True, reciprocal=Fals
     return out.view(1, 1, ht, wt) if normalised else out.view(ht, wt)
 
 
+def image_warp_resize(src_u8, M, wt, ht, out=None, normalised=True, reciprocal=False, warp_size=None, brightness_contrast=None):
+    """One image of a homography training pair in one launch: decoded uint8 image -> gray -> cv2.warpPerspective(gray, M, warp_size)
+    -> resize to (wt, ht) -> optional brightness / contrast -> [1,1,ht,wt] fp32 in [0,1] (normalised=False: [ht,wt] uint8).  No warped
+    image is materialised.  Bit-identical to matcher.cv2_resize_linear_u8(homo_data.cv2_warp_perspective_u8(cv2_gray_u8(src), M, *warp_size),
+    wt, ht), then homo_data.brightness_contrast_u8, then the division of image_gray_resize (`reciprocal` as there).
+    M: the FORWARD 3x3 matrix (source -> warped image, what cv2.warpPerspective takes), anything numpy reads as 3x3; it is inverted
+    here in fp64 and the inverse travels in the launch arguments.  A singular or non-finite M is a ValueError.
+    warp_size: (w, h) of the warped image the resize reads, default the source's size (HomoDataset.py:96).
+    brightness_contrast: None or (alpha, beta): v -> clip(trunc(fp32(v) * alpha + beta * 255), 0, 255) on the resized uint8 value.
+    M = identity at the source's size is image_gray_resize with the brightness / contrast step (image 0 of a pair).
+    src_u8, out: as image_gray_resize."""
+    import numpy as np
+    _need_cuda(src_u8, out)
+    if src_u8.dtype != torch.uint8 or src_u8.dim() not in (2, 3) or (src_u8.dim() == 3 and src_u8.shape[2] != 3):
+        raise ValueError(f'image_warp_resize: src_u8 must be a uint8 [H,W,3] or [H,W] tensor, got {src_u8.dtype} {tuple(src_u8.shape)}')
+    ch = 3 if src_u8.dim() == 3 else 1
+    hs, ws = src_u8.shape[:2]
+    wt, ht = int(wt), int(ht)
+    ww, hw = (ws, hs) if warp_size is None else (int(warp_size[0]), int(warp_size[1]))
+    if min(wt, ht, ww, hw) < 1:
+        raise ValueError(f'image_warp_resize: sizes must be positive, got target {wt} x {ht}, warp {ww} x {hw}')
+    if hs < 1 or ws < 1 or (ch == 3 and src_u8.stride(2) != 1) or (ws > 1 and src_u8.stride(1) != ch) or (hs > 1 and src_u8.stride(0) < ws * ch):
+        raise ValueError('image_warp_resize: the pixels of a source row must be contiguous (row stride >= W * channels)')
+    M = np.asarray(M.detach().cpu().numpy() if torch.is_tensor(M) else M, dtype=np.float64)
+    if M.shape != (3, 3) or not np.isfinite(M).all():
+        raise ValueError('image_warp_resize: M must be a finite 3x3 matrix')
+    try:
+        minv = np.linalg.inv(M)
+    except np.linalg.LinAlgError:
+        minv = None
+    if minv is None or not np.isfinite(minv).all():
+        raise ValueError('image_warp_resize: M is singular')
+    dtype = torch.float32 if normalised else torch.uint8
+    if out is None:
+        out = torch.empty(ht, wt, dtype=dtype, device=src_u8.device)
+    elif out.dtype != dtype or out.numel() != ht * wt or not out.is_contiguous() or out.device != src_u8.device:
+        raise ValueError(f'image_warp_resize: out must hold {ht} x {wt} contiguous {dtype} elements on {src_u8.device}')
+    stride = src_u8.stride(0) if hs > 1 else ws * ch
+    kind = _lib.GF_IMAGE_U8 if not normalised else _lib.GF_IMAGE_F32_NORMALISED_RCP if reciprocal else _lib.GF_IMAGE_F32_NORMALISED
+    bc = None
+    if brightness_contrast is not None:
+        alpha, beta = (float(v) for v in brightness_contrast)
+        if not (np.isfinite(alpha) and np.isfinite(beta)):
+            raise ValueError('image_warp_resize: brightness_contrast must be two finite numbers')
+        bc = (ctypes.c_float * 2)(alpha, beta)
+    check(_lib.lib().gf_image_warp_resize(_p(src_u8), ch, hs, ws, stride, (ctypes.c_double * 9)(*minv.reshape(-1)), hw, ww, _p(out), kind,
+                                          ht, wt, bc, ctypes.c_void_p(_stream_handle(src_u8.device))), 'gf_image_warp_resize')
+    return out.view(1, 1, ht, wt) if normalised else out.view(ht, wt)
+
+
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
 
 

@@ -1,13 +1,15 @@
 """Training entry point, the counterpart of lightning/train_homo_geoformer.py:61-130 without Lightning:
 
     python -m geoformer_amd.train.run --steps 20 --batch 4 --size 480 640
+    python -m geoformer_amd.train.run --steps 20 --batch 4 --size 480 640 --data /path/to/images
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 -m geoformer_amd.train.run ...
 
 One process per GPU (RANK / LOCAL_RANK / WORLD_SIZE from the environment), DDP over RCCL with SyncBatchNorm and
-find_unused_parameters=True, AdamW + linear warm-up + MultiStepLR with the canonical lr/batch scaling.  The
-Oxford-Paris / MegaDepth images are not available offline: batches are synthetic homography pairs (texture +
-random 4-corner warp) carrying the same keys the reference's HomoDataset provides (`H_0to1`, `H_1to0`,
-`dataset_name`); a real dataset only has to yield those keys.
+find_unused_parameters=True, AdamW + linear warm-up + MultiStepLR with the canonical lr/batch scaling.  With
+`--data DIR` the batches are homography pairs generated from the .jpg / .ppm images under DIR (train/homo_data.py,
+the counterpart of homodataset/HomoDataset.py; `--size H W` is its `size`, the rank slice comes from the process
+group).  Without it they are synthetic homography pairs (texture + random 4-corner warp) carrying the same keys
+(`H_0to1`, `H_1to0`, `dataset_name`).
 """
 import argparse
 import os
@@ -41,6 +43,13 @@ def main(argv=None):
                     help='after training: K synthetic MegaDepth-style batches through the validation step (device essential-matrix RANSAC, '
                          'epipolar errors) on RANK 0 ONLY - the other ranks wait, nothing is gathered - which prints auc@5/10/20 and '
                          'prec@5e-04 over exactly those K batches')
+    ap.add_argument('--data', default=None, metavar='DIR',
+                    help='train on homography pairs generated from the .jpg / .ppm images under DIR (train/homo_data.py: HomoPairs)')
+    ap.add_argument('--data-preprocess', default='device', choices=['host', 'device'],
+                    help="with --data: warp, resize and augmentation in one HIP launch per image ('device') or in numpy ('host'); same bits")
+    ap.add_argument('--data-seed', type=int, default=0, help='with --data: the seed of every draw (matrix, augmentation, swap, order)')
+    ap.add_argument('--data-st', type=int, default=32, help="with --data: HomoDataset's `st` (0: fixed size, portrait sources transposed)")
+    ap.add_argument('--no-augment', action='store_true', help='with --data: no brightness / contrast augmentation')
     ap.add_argument('--report', default=None,
                     help='rank 0 writes a JSON report: per-step losses averaged over the ranks, whether the parameters of all ranks '
                          'are bit-identical after the last step, and a float64 checksum per parameter')
@@ -77,13 +86,21 @@ def main(argv=None):
         tcfg.update(gradient_clipping=0.0)
     step = TrainStep(model, trainer_cfg=tcfg or None, batch_size=args.batch, distributed=ddp, fused_coarse_loss=args.fused_coarse_loss,
                      precision=args.precision, hip_backward=args.hip_backward)
+    data_iter = None
+    if args.data:
+        from .homo_data import HomoPairs
+        pairs = HomoPairs(args.data, size=tuple(args.size), st=args.data_st, rank=rank, world_size=world if world > 1 else None,
+                          seed=args.data_seed, device=dev, preprocess=args.data_preprocess, augment=not args.no_augment)
+        data_iter = epochs_of(pairs, args.batch)
     t0 = t1 = time.perf_counter()
     losses = []
     for it in range(args.steps):
         if it == 1:                               # the first step carries MIOpen's algorithm search
             torch.cuda.synchronize()
             t1 = time.perf_counter()
-        if args.global_batch_seed is None:
+        if data_iter is not None:
+            batch = next(data_iter)
+        elif args.global_batch_seed is None:
             batch = synthetic_homography_batch(args.batch, tuple(args.size), seed=1000 * rank + it, device=dev)
         else:
             batch = rank_slice_of_global_batch(args.batch, world, rank, tuple(args.size), args.global_batch_seed + it, args.dup, dev)
@@ -94,8 +111,8 @@ def main(argv=None):
         if rank == 0:
             s = batch['loss_scalars']
             print(f'step {it:4d} loss {float(loss):.4f} (c {float(s["loss_c"]):.4f} d {float(s["loss_d"]):.4f} f {float(s["loss_f"]):.4f}) '
-                  f'lr {step.optimizer.param_groups[0]["lr"]:.2e} matches {len(batch["b_ids"])} gt {int(batch["conf_matrix_gt"].sum())}',
-                  flush=True)
+                  f'lr {step.optimizer.param_groups[0]["lr"]:.2e} matches {len(batch["b_ids"])} gt {int(batch["conf_matrix_gt"].sum())}' +
+                  (f' pairs {",".join(batch["pair_names"][0])}' if data_iter is not None else ''), flush=True)
     torch.cuda.synchronize()
     if rank == 0:
         now = time.perf_counter()
@@ -120,6 +137,19 @@ def main(argv=None):
     if ddp:
         torch.distributed.destroy_process_group()
     return float(loss)
+
+
+def epochs_of(pairs, batch_size):
+    """Batches of a HomoPairs dataset without end: epoch after epoch, full batches of one shape each."""
+    epoch = 0
+    while True:
+        n = 0
+        for indices in pairs.batches(batch_size, epoch, drop_last=True):
+            n += 1
+            yield pairs.batch(indices, epoch)
+        if n == 0:
+            raise ValueError(f'--data: {len(pairs)} images under {pairs.img_dir} give no full batch of {batch_size} pairs of one shape')
+        epoch += 1
 
 
 def rank_slice_of_global_batch(batch, world, rank, hw, seed, dup, device):

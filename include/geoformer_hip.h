@@ -560,6 +560,28 @@ typedef enum { GF_IMAGE_U8 = 0, GF_IMAGE_F32_NORMALISED = 1, GF_IMAGE_F32_NORMAL
 int gf_image_gray_resize(const void* src, int channels, int hs, int ws, long long src_row_stride_bytes, void* dst, int dst_kind,
                          int ht, int wt, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * One image of a homography training pair, one launch: decoded uint8 image -> gray -> perspective warp -> resize ->
+ * brightness / contrast -> the tensor the model consumes; no warped image is materialised
+ * replaces get_pair (homodataset/HomoDataset.py:83-123): cv2.warpPerspective(image, M, (warp_w, warp_h)) at the warp's own
+ *          resolution (INTER_LINEAR, BORDER_CONSTANT 0), cv2.resize of the uint8 result, the brightness / contrast group of aug_func
+ *   src, channels, hs, ws, src_row_stride_bytes, dst, dst_kind, ht, wt   as gf_image_gray_resize; dst holds ht * wt contiguous elements
+ *   minv  HOST pointer to 9 doubles, row-major: the INVERSE of the forward matrix M, inverted by the caller in fp64.  Copied into the
+ *         launch's arguments (no device buffer, nothing to keep alive).  Every entry must be finite.
+ *   warp_h, warp_w  size of the warp's destination image (the reference passes the source's size); the resize reads THAT image
+ *   brightness_contrast  NULL, or a HOST pointer to {alpha, beta} (fp32): the resized uint8 value v becomes
+ *         clip(trunc(fp32(v) * alpha + beta * 255), 0, 255) before the division (albumentations' uint8 look-up-table rule)
+ *   The warp arithmetic is stated in geoformer_amd/csrc/warp_spec.h (OpenCV's 8-bit path: positions rounded to 1/32 pixel, integer
+ *   bilinear weights, a tap outside the source counts 0; the numerators are evaluated per pixel, not incrementally per block - OpenCV
+ *   parity is unpinned there).  Bit-identical to geoformer_amd.matcher.cv2_resize_linear_u8(geoformer_amd.train.homo_data.
+ *   cv2_warp_perspective_u8(cv2_gray_u8(src), M, warp_w, warp_h), wt, ht) followed by homo_data.brightness_contrast_u8.
+ *   minv == identity with warp_h == hs and warp_w == ws takes gf_image_gray_resize's path (same bits, no warp arithmetic): image 0 of a pair.
+ *   No workspace.
+ * ------------------------------------------------------------------------------------------ */
+int gf_image_warp_resize(const void* src, int channels, int hs, int ws, long long src_row_stride_bytes, const double* minv,
+                         int warp_h, int warp_w, void* dst, int dst_kind, int ht, int wt, const float* brightness_contrast,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif
