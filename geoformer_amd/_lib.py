@@ -131,6 +131,11 @@ SIGNATURES = {
     'gf_image_gray_resize': (c_int, [c_void_p, c_int, c_int, c_int, ctypes.c_longlong, c_void_p, c_int, c_int, c_int, c_void_p]),
     'gf_image_warp_resize': (c_int, [c_void_p, c_int, c_int, c_int, ctypes.c_longlong, ctypes.POINTER(ctypes.c_double), c_int, c_int, c_void_p,
                                      c_int, c_int, c_int, ctypes.POINTER(c_float), c_void_p]),
+    'gf_pos_encode_ptrs': (c_int, [c_void_p, c_int, c_long, c_long, c_long, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                   c_void_p]),
+    'gf_fine_gather_ptrs': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                    c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                    c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
 

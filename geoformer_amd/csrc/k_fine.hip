@@ -16,8 +16,8 @@
 namespace {
 
 struct FgArgs {
-    const void* f0;          // fine maps viewed as [N, C, H, W] with element strides
-    const void* f1;
+    const void* f0;          // fine maps viewed as [N, C, H, W] with element strides.  TBL forms (gf_fine_gather_ptrs): f0 / f1 are
+    const void* f1;          // device tables of N per-sample base addresses (const void* const*), s0n / s1n unused
     long s0n, s0c, s0h, s0w, s1n, s1c, s1h, s1w;
     int H0, W0, H1, W1, C;   // fine map sizes
     const void* c0;          // coarse (geo) features [N, L, CC], [N, S, CC]
@@ -31,15 +31,24 @@ struct FgArgs {
     void* ccat;              // [2M][CC]
 };
 
+// Where sample b of one side starts: maps + b * sn (TBL = false), or entry b of a table in device memory (TBL = true) - the one
+// difference between gf_fine_gather and gf_fine_gather_ptrs.  b must be uniform (a scalar register): the entry is then one scalar
+// 8-byte load per workgroup / wave, issued once in front of the window loop.
+template <typename TF, bool TBL>
+__device__ __forceinline__ const TF* fg_sample(const void* maps, int b) {
+    if constexpr (TBL) return (const TF*)((const void* const*)maps)[b];
+    else return (const TF*)maps;      // + b * sn: added where the element offset is formed, as before the table forms existed
+}
+
 // one workgroup per (match, side): thread c < C copies channel c of the 25 window positions
-template <typename TF, typename T>
+template <typename TF, typename T, bool TBL>
 __global__ __launch_bounds__(256) void fine_gather(FgArgs a) {
     const int m = blockIdx.x, side = blockIdx.y, t = threadIdx.x;
     const int b = (int)a.b_ids[m];
     const int cell = (int)(side ? a.j_ids[m] : a.i_ids[m]);
     const int wc = side ? a.w1c : a.w0c;
     const int Hf = side ? a.H1 : a.H0, Wf = side ? a.W1 : a.W0;
-    const TF* f = (const TF*)(side ? a.f1 : a.f0);
+    const TF* f = fg_sample<TF, TBL>(side ? a.f1 : a.f0, b);      // b = b_ids[blockIdx.x]: uniform
     const long sn = side ? a.s1n : a.s0n, sc = side ? a.s1c : a.s0c, sh = side ? a.s1h : a.s0h, sw = side ? a.s1w : a.s0w;
     const int cy = (cell / wc) * a.stride - a.W / 2, cx = (cell % wc) * a.stride - a.W / 2;
     T* out = (T*)a.win + ((size_t)side * a.M + m) * a.W * a.W * a.C;
@@ -47,7 +56,7 @@ __global__ __launch_bounds__(256) void fine_gather(FgArgs a) {
         for (int k = 0; k < a.W * a.W; ++k) {
             const int y = cy + k / a.W, x = cx + k % a.W;
             float v = 0.f;                                        // zero padding of F.unfold
-            if (y >= 0 && y < Hf && x >= 0 && x < Wf) v = gf_to_float(f[b * sn + t * sc + y * sh + x * sw]);
+            if (y >= 0 && y < Hf && x >= 0 && x < Wf) v = gf_to_float(f[(TBL ? 0 : b * sn) + t * sc + y * sh + x * sw]);
             out[(size_t)k * a.C + t] = gf_from_float<T>(v);
         }
     }
@@ -80,17 +89,20 @@ __device__ __forceinline__ v4u fg_convert8(v4u v) {
 // bf16 value above 65504 becomes +-inf in fp16, one below fp16's subnormal spacing rounds to nearest even (to a subnormal or to
 // a signed zero).  The fp16 mode has the same range through its own backbone.  Same bytes per match as the copy: 16-byte loads
 // and stores either way.  The coarse row is in T already and stays a copy.
-template <typename TF, typename T>
+template <typename TF, typename T, bool TBL>
 __global__ __launch_bounds__(256) void fine_gather_rows(FgArgs a) {
     static_assert(sizeof(TF) == 2 && sizeof(T) == 2, "16-byte pieces of 8 elements on both sides");
-    const int lane = threadIdx.x & 63, u = blockIdx.x * 4 + (threadIdx.x >> 6);
+    // TBL: the wave's unit is the same in all 64 lanes but the compiler cannot know (it comes from threadIdx): it goes through
+    // v_readfirstlane, so that side, match and sample index are scalars and the table entry is ONE scalar load per wave in front of
+    // the loop - not 64 lanes fetching one address
+    const int lane = threadIdx.x & 63, u0 = blockIdx.x * 4 + (threadIdx.x >> 6), u = TBL ? __builtin_amdgcn_readfirstlane(u0) : u0;
     if (u >= 2 * a.M) return;
     const int side = u >= a.M, m = side ? u - a.M : u;
     const int b = (int)a.b_ids[m];
     const int cell = (int)(side ? a.j_ids[m] : a.i_ids[m]);
     const int wc = side ? a.w1c : a.w0c;
     const int Hf = side ? a.H1 : a.H0, Wf = side ? a.W1 : a.W0;
-    const TF* f = (const TF*)(side ? a.f1 : a.f0);
+    const TF* f = fg_sample<TF, TBL>(side ? a.f1 : a.f0, b);
     const long sn = side ? a.s1n : a.s0n, sh = side ? a.s1h : a.s0h, sw = side ? a.s1w : a.s0w;
     const int cy = (cell / wc) * a.stride - a.W / 2, cx = (cell % wc) * a.stride - a.W / 2;
     const int ppp = a.C / 8, pieces = a.W * a.W * ppp;                  // 16-byte pieces per position / per window
@@ -99,7 +111,7 @@ __global__ __launch_bounds__(256) void fine_gather_rows(FgArgs a) {
     for (int e = lane; e < pieces; e += 64) {
         const int k = e / ppp, c8 = (e - k * ppp) * 8, y = cy + k / a.W, x = cx + k % a.W;
         v4u v = zero;
-        if (y >= 0 && y < Hf && x >= 0 && x < Wf) v = fg_convert8<TF, T>(*reinterpret_cast<const v4u*>(f + b * sn + y * sh + x * sw + c8));
+        if (y >= 0 && y < Hf && x >= 0 && x < Wf) v = fg_convert8<TF, T>(*reinterpret_cast<const v4u*>(f + (TBL ? 0 : b * sn) + y * sh + x * sw + c8));
         *reinterpret_cast<v4u*>(out + (size_t)k * a.C + c8) = v;
     }
     const T* cf = (const T*)(side ? a.c1 : a.c0) + ((size_t)b * (side ? a.S : a.L) + cell) * a.CC;
@@ -332,27 +344,37 @@ __global__ __launch_bounds__(1024) void fine_compact(FmArgs a) {
     a.m_bids[pos] = b;
 }
 
-template <typename TF, typename T>
-int fg_launch(const FgArgs& a, hipStream_t st) {
+// feat_align (TBL): the largest power of two, in bytes, that divides EVERY entry of both tables - the caller built them and knows
+template <typename TF, typename T, bool TBL>
+int fg_launch(const FgArgs& a, hipStream_t st, unsigned feat_align) {
     if constexpr (sizeof(TF) == 2 && sizeof(T) == 2) {
-        const bool rows16 = a.s0c == 1 && a.s1c == 1 && a.C % 8 == 0 && a.CC % 8 == 0 && (uintptr_t)a.f0 % 16 == 0 && (uintptr_t)a.f1 % 16 == 0 &&
+        const bool maps16 = TBL ? feat_align % 16 == 0
+                                : (uintptr_t)a.f0 % 16 == 0 && (uintptr_t)a.f1 % 16 == 0 && a.s0n % 8 == 0 && a.s1n % 8 == 0;
+        const bool rows16 = a.s0c == 1 && a.s1c == 1 && a.C % 8 == 0 && a.CC % 8 == 0 && maps16 &&
                             (uintptr_t)a.c0 % 16 == 0 && (uintptr_t)a.c1 % 16 == 0 && (uintptr_t)a.win % 16 == 0 && (uintptr_t)a.ccat % 16 == 0 &&
-                            a.s0n % 8 == 0 && a.s0h % 8 == 0 && a.s0w % 8 == 0 && a.s1n % 8 == 0 && a.s1h % 8 == 0 && a.s1w % 8 == 0;
+                            a.s0h % 8 == 0 && a.s0w % 8 == 0 && a.s1h % 8 == 0 && a.s1w % 8 == 0;
         if (rows16) {
-            fine_gather_rows<TF, T><<<(2 * a.M + 3) / 4, 256, 0, st>>>(a);
+            fine_gather_rows<TF, T, TBL><<<(2 * a.M + 3) / 4, 256, 0, st>>>(a);
             GF_CHECK_LAUNCH();
             return GF_OK;
         }
     }
-    fine_gather<TF, T><<<dim3(a.M, 2), 256, 0, st>>>(a);
+    fine_gather<TF, T, TBL><<<dim3(a.M, 2), 256, 0, st>>>(a);
     GF_CHECK_LAUNCH();
     return GF_OK;
 }
 
-template <typename TF>
-int fg_launch_to(int dtype, const FgArgs& a, hipStream_t st) {
-    return dtype == GF_F32 ? fg_launch<TF, float>(a, st)
-                           : dtype == GF_F16 ? fg_launch<TF, _Float16>(a, st) : fg_launch<TF, gf_bf16>(a, st);
+template <typename TF, bool TBL>
+int fg_launch_to(int dtype, const FgArgs& a, hipStream_t st, unsigned feat_align) {
+    return dtype == GF_F32 ? fg_launch<TF, float, TBL>(a, st, feat_align)
+                           : dtype == GF_F16 ? fg_launch<TF, _Float16, TBL>(a, st, feat_align) : fg_launch<TF, gf_bf16, TBL>(a, st, feat_align);
+}
+
+template <bool TBL>
+int fg_dispatch(int feat_dtype, int dtype, const FgArgs& a, hipStream_t st, unsigned feat_align) {
+    if (feat_dtype == GF_F32) return fg_launch_to<float, TBL>(dtype, a, st, feat_align);
+    if (feat_dtype == GF_F16) return fg_launch_to<_Float16, TBL>(dtype, a, st, feat_align);
+    return fg_launch_to<gf_bf16, TBL>(dtype, a, st, feat_align);
 }
 
 }   // namespace
@@ -369,10 +391,24 @@ extern "C" int gf_fine_gather(const void* feat_f0, const void* feat_f1, int feat
     FgArgs a{feat_f0, feat_f1, strides0[0], strides0[1], strides0[2], strides0[3], strides1[0], strides1[1], strides1[2],
              strides1[3], H0, W0, H1, W1, C, feat_c0, feat_c1, L, S, CC, b_ids, i_ids, j_ids, M, w0c, w1c, stride, window,
              win_out, ccat_out};
-    hipStream_t st = (hipStream_t)stream;
-    if (feat_dtype == GF_F32) return fg_launch_to<float>(dtype, a, st);
-    if (feat_dtype == GF_F16) return fg_launch_to<_Float16>(dtype, a, st);
-    return fg_launch_to<gf_bf16>(dtype, a, st);
+    return fg_dispatch<false>(feat_dtype, dtype, a, (hipStream_t)stream, 0);
+}
+
+extern "C" int gf_fine_gather_ptrs(const void* const* f0_table, const void* const* f1_table, int N, int feat_dtype, int feat_align,
+                                   const long* strides0, const long* strides1, int H0, int W0, int H1, int W1, int C,
+                                   const void* feat_c0, const void* feat_c1, int dtype, int L, int S, int CC, const int64_t* b_ids,
+                                   const int64_t* i_ids, const int64_t* j_ids, int M, int w0c, int w1c, int stride, int window,
+                                   void* win_out, void* ccat_out, void* stream) {
+    GF_CHECK_ARG(f0_table && f1_table && strides0 && strides1 && feat_c0 && feat_c1 && b_ids && i_ids && j_ids && win_out && ccat_out, "null pointer");
+    GF_CHECK_ARG(N > 0, "empty table");
+    GF_CHECK_ARG(M > 0, "M must be > 0 (the M == 0 early return of fine_preprocess.py:35-38 is the caller's)");
+    GF_CHECK_ARG(C > 0 && C <= 256 && window > 0 && stride > 0 && w0c > 0 && w1c > 0, "bad sizes");
+    GF_CHECK_ARG(feat_align > 0 && (feat_align & (feat_align - 1)) == 0, "feat_align must be a power of two");
+    GF_CHECK_ARG(feat_dtype >= GF_F32 && feat_dtype <= GF_BF16 && dtype >= GF_F32 && dtype <= GF_BF16, "bad dtype");
+    FgArgs a{f0_table, f1_table, 0, strides0[0], strides0[1], strides0[2], 0, strides1[0], strides1[1], strides1[2],
+             H0, W0, H1, W1, C, feat_c0, feat_c1, L, S, CC, b_ids, i_ids, j_ids, M, w0c, w1c, stride, window,
+             win_out, ccat_out};
+    return fg_dispatch<true>(feat_dtype, dtype, a, (hipStream_t)stream, (unsigned)feat_align);
 }
 
 extern "C" size_t gf_fine_match_workspace_bytes(int M) {

@@ -14,17 +14,19 @@ build container, so the restatement is pinned by hand-derived vectors (tests/tes
 output.  The homography of the HPatches metric is estimated from the fine matches by the device RANSAC
 (`ops.ransac_homography(..., thr=ransac_thres, integer_keypoints=False, min_points=4)`).
 """
+import collections
 import glob
 import os
+import threading
 import time
-from typing import Optional
+from typing import NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
 
 from . import ops
 from .model.cvpr_ds_config import get_default_cfg
-from .model.full_model import PRECISIONS, GeoFormer
+from .model.full_model import PRECISIONS, GeoFormer, ImageFeatures
 from .model.geo_config import get_cfg_model
 
 
@@ -177,14 +179,129 @@ def load_gray_scale_tensor(im_path, device, imsize=None, dfactor=8, value_to_sca
     return t / 255.0, scale
 
 
+# ---------------------------------------------------------------------------------------------
+# features once, matches many times: the per-image half of a match, kept by key
+# ---------------------------------------------------------------------------------------------
+class StoredImage(NamedTuple):
+    """One extracted image: the backbone's maps (GeoFormer.extract_features) and the resize ratios load_im returned with it."""
+    features: ImageFeatures
+    scale: Tuple[float, float]       # (wo / wt, ho / ht)
+
+    @property
+    def nbytes(self):
+        return self.features.nbytes
+
+
+class FeatureStore:
+    """key -> record with least-recently-used eviction under an optional byte budget (max_bytes=None: unbounded).  The matcher's
+    keys are (path, preprocessing signature).  `extractions` counts the records made (misses), `hits` the lookups served from
+    the store.  A lock guards lookup, insert and evict: the HPatches loop may feed the GPU from two host pipelines; the extraction
+    itself runs outside the lock (two threads missing the same key both extract, the first insert wins, both count)."""
+
+    def __init__(self, max_bytes: Optional[int] = None):
+        if max_bytes is not None and max_bytes < 0:
+            raise ValueError('max_bytes must be None (unbounded) or >= 0')
+        self.max_bytes = max_bytes
+        self.extractions = self.hits = self.evictions = 0
+        self.nbytes = 0
+        self._items = collections.OrderedDict()     # key -> (record, nbytes), least recently used first
+        self._lock = threading.Lock()
+
+    def __len__(self):
+        return len(self._items)
+
+    def __contains__(self, key):
+        return key in self._items
+
+    def keys(self):
+        """Least recently used first."""
+        return list(self._items)
+
+    def get(self, key):
+        with self._lock:
+            item = self._items.get(key)
+            if item is None:
+                return None
+            self._items.move_to_end(key)
+            self.hits += 1
+            return item[0]
+
+    def put(self, key, record, nbytes=None):
+        """Inserts `record` as the most recently used entry (an entry already under `key` is kept and returned instead), then evicts
+        from the least recently used end until the budget holds again.  The new entry itself stays, whatever its size."""
+        nbytes = int(record.nbytes if nbytes is None else nbytes)
+        with self._lock:
+            self.extractions += 1
+            if key in self._items:
+                self._items.move_to_end(key)
+                return self._items[key][0]
+            self._items[key] = (record, nbytes)
+            self.nbytes += nbytes
+            while self.max_bytes is not None and self.nbytes > self.max_bytes and len(self._items) > 1:
+                # An evicted record may still be read by launches that are enqueued but have not run.  That is safe: extraction and
+                # matching are enqueued on the current stream, and the caching allocator hands a freed block to later work on the
+                # same stream only - work that runs after those launches.  (Callers also hold the records of the batch in flight.)
+                _, (_, freed) = self._items.popitem(last=False)
+                self.nbytes -= freed
+                self.evictions += 1
+            return record
+
+    def get_or_extract(self, key, extract):
+        rec = self.get(key)
+        return rec if rec is not None else self.put(key, extract())
+
+    def clear(self):
+        with self._lock:
+            self._items.clear()
+            self.nbytes = 0
+
+
+def group_pairs(shapes, batch):
+    """shapes[k] = any hashable description of pair k's (shape0, shape1).  -> list of index lists, each of one shape group and at most
+    `batch` long: groups in order of first appearance, a group's pairs in input order, its last batch possibly short."""
+    if batch < 1:
+        raise ValueError('batch must be >= 1')
+    groups = collections.OrderedDict()
+    for k, sh in enumerate(shapes):
+        groups.setdefault(sh, []).append(k)
+    return [idx[s:s + batch] for idx in groups.values() for s in range(0, len(idx), batch)]
+
+
+def read_pair_list(list_path):
+    """Two image paths per line (whitespace separated; blank lines and lines starting with '#' are skipped); a relative path is
+    relative to the directory of the list file."""
+    base = os.path.dirname(os.path.abspath(list_path))
+    pairs = []
+    with open(list_path) as f:
+        for no, line in enumerate(f, 1):
+            parts = line.split()
+            if not parts or parts[0].startswith('#'):
+                continue
+            if len(parts) != 2:
+                raise ValueError(f'{list_path}:{no}: expected two image paths, got {len(parts)} fields')
+            pairs.append(tuple(p if os.path.isabs(p) else os.path.normpath(os.path.join(base, p)) for p in parts))
+    return pairs
+
+
+IMAGE_EXTENSIONS = ('.png', '.jpg', '.jpeg', '.ppm', '.pgm', '.bmp', '.tif', '.tiff')
+
+
+def all_pairs(image_dir):
+    """Every pair (i < j) of the image files directly under `image_dir`, sorted by name."""
+    names = sorted(n for n in os.listdir(image_dir) if n.lower().endswith(IMAGE_EXTENSIONS))
+    paths = [os.path.join(image_dir, n) for n in names]
+    return [(paths[i], paths[j]) for i in range(len(paths)) for j in range(i + 1, len(paths))]
+
+
 class GeoFormerMatcher:
     def __init__(self, imsize, match_threshold, no_match_upscale=False, ckpt=None, device='cuda', precision='fp32',
-                 miopen_search=False, preprocess='host'):
+                 miopen_search=False, preprocess='host', cache_bytes=None):
         """precision / miopen_search / preprocess are additions: 'fp16' is the fast mode ('bf16', 'bf16_fp16': GeoFormer.set_precision);
         miopen_search=True lets MIOpen search its convolution algorithms once per new image shape (seconds each, ~25 % faster
         backbone afterwards: 6.8 -> 5.2 ms per 480x640 pair) - worth it when a dataset repeats a few shapes; preprocess='device'
         moves gray conversion, resize and normalisation of the decoded images from numpy to one kernel per image
-        (load_gray_scale_tensor), same bits."""
+        (load_gray_scale_tensor), same bits.  cache_bytes: byte budget of the feature store behind extract / match_many (None: unbounded)."""
+        self.store = FeatureStore(cache_bytes)
         if preprocess not in PREPROCESS:
             raise ValueError(f'preprocess must be one of {PREPROCESS}, got {preprocess!r}')
         if preprocess == 'device' and torch.device(device).type != 'cuda':
@@ -232,6 +349,74 @@ class GeoFormerMatcher:
         return upscale * matches, sc1 * kpts1, sc2 * kpts2, scores
 
     __call__ = match_pairs
+
+    # -- features once, matches many times (GeoFormer.extract_features / match_features behind a FeatureStore)
+    def _store_key(self, im_path):
+        return (im_path, (self.imsize, self.preprocess, self.model.precision, str(self.model.backbone_dtype)))
+
+    def resized_shape(self, im_path):
+        """(H, W) of the tensor load_im makes of the file, from the file's header alone."""
+        from PIL import Image
+        with Image.open(im_path) as im:
+            wo, ho = im.size
+        wt, ht, _ = resize_im(wo, ho, imsize=self.imsize, dfactor=8, value_to_scale=min)
+        return ht, wt
+
+    def extract(self, im_path, slot=0) -> StoredImage:
+        """The image's feature record (maps + resize ratios) through the store: loaded (preprocess = host or device, as match_pairs
+        loads it) and run through the backbone on a miss, the kept record on a hit."""
+        def make():
+            gray, scale = self.load_im(im_path, slot=slot)
+            with torch.no_grad():
+                return StoredImage(self.model.extract_features(gray)[0], scale)
+        return self.store.get_or_extract(self._store_key(im_path), make)
+
+    def _results(self, data, recs0, recs1):
+        """The model's batch output -> one match_pairs-style tuple per pair, split by m_bids."""
+        k0, k1 = data['mkpts0_f'].cpu().numpy(), data['mkpts1_f'].cpu().numpy()
+        scores, bids = data['mconf'].cpu().numpy(), data['m_bids'].cpu().numpy()
+        out = []
+        for n, (r0, r1) in enumerate(zip(recs0, recs1)):
+            sel = bids == n
+            kpts1, kpts2, sc = k0[sel], k1[sel], scores[sel]
+            matches = np.concatenate([kpts1, kpts2], axis=1)
+            upscale = np.array([r0.scale + r1.scale])
+            if self.no_match_upscale:
+                out.append((matches, kpts1, kpts2, sc, upscale.squeeze(0)))
+            else:
+                out.append((upscale * matches, r0.scale * kpts1, r1.scale * kpts2, sc))
+        return out
+
+    def match_features(self, rec0: StoredImage, rec1: StoredImage):
+        """match_pairs from two kept records: same return convention (no_match_upscale included)."""
+        with torch.no_grad():
+            data = self.model.match_features([rec0.features], [rec1.features])
+        return self._results(data, [rec0], [rec1])[0]
+
+    def match_pairs_cached(self, im1_path, im2_path):
+        """match_pairs with both images going through the store (an image that recurs is extracted once)."""
+        return self.match_features(self.extract(im1_path, slot=0), self.extract(im2_path, slot=1))
+
+    def match_many(self, pairs, batch=8):
+        """[(path0, path1), ...] -> one match_pairs-style tuple per pair, in the order of `pairs`.  Pairs are grouped by their two
+        resized shapes and run `batch` at a time through GeoFormer.match_features; every image is extracted once (once per stay in the
+        store, under a byte budget).  A pair's numbers are those of the model on ITS BATCH - as with any batched `forward`, the device
+        RANSAC draws its samples per position in the batch - so they equal match_pairs' exactly for batches of one pair."""
+        pairs = [tuple(p) for p in pairs]
+        shape = {}
+        for p in pairs:
+            for path in p:
+                if path not in shape:
+                    shape[path] = self.resized_shape(path)
+        results = [None] * len(pairs)
+        for idx in group_pairs([(shape[a], shape[b]) for a, b in pairs], batch):
+            recs0 = [self.extract(pairs[k][0], slot=0) for k in idx]       # held here: eviction cannot free a map of the batch in flight
+            recs1 = [self.extract(pairs[k][1], slot=1) for k in idx]
+            with torch.no_grad():
+                data = self.model.match_features([r.features for r in recs0], [r.features for r in recs1])
+            for k, res in zip(idx, self._results(data, recs0, recs1)):
+                results[k] = res
+        return results
 
 
 # ---------------------------------------------------------------------------------------------
@@ -309,13 +494,16 @@ def hpatches_pairs(data_root, max_seqs: Optional[int] = None):
 
 
 def eval_hpatches(matcher, data_root, ransac_thres=3, thres=(1, 3, 5, 10), scale_H=True, max_seqs: Optional[int] = None,
-                  log=print):
+                  log=print, reuse_features=False):
     """Homography-estimation AUC over HPatches sequences (pairs 1 -> 2..6), the protocol of
     hpatches_helper.eval_hpatches with task='homography', h_solver='cv'.
 
     Pairs are independent: under torch.distributed (one process per GPU) the pair list is cut into contiguous
     per-rank blocks by `shard.run_sharded` and every rank ends up with the summaries of ALL pairs, so the metric
-    is identical on every rank and to a single-process run."""
+    is identical on every rank and to a single-process run.
+
+    reuse_features: the pairs go through the matcher's feature store (`match_pairs_cached`), so image 1 of a sequence is extracted
+    once instead of five times."""
     from PIL import Image
     from .shard import run_sharded
 
@@ -325,7 +513,7 @@ def eval_hpatches(matcher, data_root, ransac_thres=3, thres=(1, 3, 5, 10), scale
             H_gt = np.loadtxt(hfile)
             scale = np.ones(4)
             t0 = time.time()
-            res = matcher(im1, im2)
+            res = matcher.match_pairs_cached(im1, im2) if reuse_features else matcher(im1, im2)
             dt = time.time() - t0
             matches = res[0]
             if scale_H and len(res) > 4:       # matches stay in resized coordinates: move the GT homography there
@@ -359,14 +547,16 @@ def eval_hpatches(matcher, data_root, ransac_thres=3, thres=(1, 3, 5, 10), scale
 # ---------------------------------------------------------------------------------------------
 # command line: the counterparts of `python inference.py` and `python eval_Hpatches.py`
 #   python -m geoformer_amd.matcher match im1 im2 [--ckpt saved_ckpt/geoformer.ckpt] [--out matches.npz] [--preprocess device]
-#   python -m geoformer_amd.matcher hpatches /path/to/hpatches-sequences-release [--ckpt ...] [--preprocess device]
+#   python -m geoformer_amd.matcher hpatches /path/to/hpatches-sequences-release [--ckpt ...] [--preprocess device] [--reuse-features]
+#   python -m geoformer_amd.matcher pairs LIST | --all-pairs DIR  [--out DIR] [--batch B] [--cache-gb G]      (no reference counterpart)
 # ---------------------------------------------------------------------------------------------
 def build_parser():
     """Defaults follow the reference per sub-command: `match` = inference.py:107 (imsize 640, matches scaled back to the
     original images); `hpatches` = eval_configs/geoformer.yml:7-11 with eval_Hpatches.py:96-100 (imsize 480, match
     threshold 0.2, no_match_upscale True -> the ground-truth homography is moved into resized coordinates, RANSAC
     threshold 3).  Under `python -m torch.distributed.run --nproc-per-node N -m geoformer_amd.matcher hpatches ...` the
-    pair list is sharded over the N GPUs (shard.run_sharded)."""
+    pair list is sharded over the N GPUs (shard.run_sharded).  `pairs` matches a list of pairs with every image's backbone pass run
+    once (GeoFormerMatcher.match_many); its defaults are `match`'s."""
     import argparse
     ap = argparse.ArgumentParser(prog='python -m geoformer_amd.matcher')
     sub = ap.add_subparsers(dest='cmd', required=True)
@@ -381,7 +571,20 @@ def build_parser():
     h.add_argument('--match-upscale', dest='no_match_upscale', action='store_false',
                    help='scale matches back to the original images instead of moving the GT homography (reference: off)')
     h.set_defaults(no_match_upscale=True)
-    for p in (m, h):
+    h.add_argument('--reuse-features', action='store_true',
+                   help="keep each image's backbone features in the feature store: image 1 of a sequence is extracted once, not five times")
+    q = sub.add_parser('pairs', help='match many pairs, extracting the features of every image once')
+    q.add_argument('list', nargs='?', default=None, help='text file with two image paths per line (relative paths: relative to the file)')
+    q.add_argument('--all-pairs', metavar='DIR', default=None, help='instead of a list: every pair of the images under DIR, sorted by name')
+    q.add_argument('--out', default=None, help='directory for one .npz per pair (keys as `match --out`: matches, kpts1, kpts2, scores)')
+    q.add_argument('--batch', type=int, default=8, help='pairs of equal shapes matched per model call')
+    q.add_argument('--imsize', type=int, default=640)
+    q.add_argument('--no-match-upscale', action='store_true')
+    for p in (h, q):
+        p.add_argument('--cache-gb', type=float, default=None,
+                       help='byte budget of the feature store in GB: least recently used images are dropped and extracted again when '
+                            'needed (default: unbounded for `pairs`, 2 for `hpatches --reuse-features`)')
+    for p in (m, h, q):
         p.add_argument('--ckpt', default=None)
         p.add_argument('--match-threshold', type=float, default=0.2)
         p.add_argument('--precision', choices=PRECISIONS, default='fp16',
@@ -396,16 +599,33 @@ def build_parser():
 
 
 def main(argv=None):
-    """`python -m geoformer_amd.matcher match|hpatches ...` (arguments: build_parser)."""
+    """`python -m geoformer_amd.matcher match|hpatches|pairs ...` (arguments: build_parser)."""
     args = build_parser().parse_args(argv)
     world = int(os.environ.get('WORLD_SIZE', '1'))
     local = int(os.environ.get('LOCAL_RANK', '0'))
     if world > 1:
         torch.cuda.set_device(local)
         torch.distributed.init_process_group('nccl', device_id=torch.device('cuda', local))
+    if args.cmd == 'pairs' and (args.list is None) == (args.all_pairs is None):
+        raise SystemExit('pairs: give either a pair list or --all-pairs DIR')
+    cache_gb = getattr(args, 'cache_gb', None)
+    if args.cmd == 'hpatches' and args.reuse_features and cache_gb is None:
+        cache_gb = 2.0             # only image 1 of the current sequence is ever asked for again: no reason to keep the whole dataset
     matcher = GeoFormerMatcher(args.imsize, args.match_threshold, args.no_match_upscale, args.ckpt, device=f'cuda:{local}',
-                               precision=args.precision, preprocess=args.preprocess)
-    if args.cmd == 'match':
+                               precision=args.precision, preprocess=args.preprocess,
+                               cache_bytes=None if cache_gb is None else int(cache_gb * 2 ** 30))
+    if args.cmd == 'pairs':
+        pairs = read_pair_list(args.list) if args.list is not None else all_pairs(args.all_pairs)
+        results = matcher.match_many(pairs, batch=args.batch)
+        if args.out:
+            os.makedirs(args.out, exist_ok=True)
+        for k, ((p0, p1), res) in enumerate(zip(pairs, results)):
+            if args.out:
+                stem = '_'.join(os.path.splitext(os.path.basename(p))[0] for p in (p0, p1))
+                np.savez(os.path.join(args.out, f'{k:05d}_{stem}.npz'), matches=res[0], kpts1=res[1], kpts2=res[2], scores=res[3])
+        st = matcher.store
+        print(f'{matcher.name}: {len(pairs)} pairs, {sum(len(r[0]) for r in results)} matches, {st.extractions} extractions, {st.hits} store hits')
+    elif args.cmd == 'match':
         res = matcher(args.im1, args.im2)
         print(f'{matcher.name}: {len(res[0])} matches')
         if args.out:
@@ -413,7 +633,9 @@ def main(argv=None):
     else:
         quiet = int(os.environ.get('RANK', '0')) != 0
         out = eval_hpatches(matcher, args.root, ransac_thres=args.ransac_thres, max_seqs=args.max_seqs,
-                            scale_H=matcher.no_match_upscale, log=(lambda s: None) if quiet else print)
+                            scale_H=matcher.no_match_upscale, log=(lambda s: None) if quiet else print, reuse_features=args.reuse_features)
+        if not quiet and args.reuse_features:
+            print(f'feature store: {matcher.store.extractions} extractions, {matcher.store.hits} hits')
         if not quiet:
             print({k: (v.tolist() if hasattr(v, 'tolist') else v) for k, v in out.items()})
     if world > 1:

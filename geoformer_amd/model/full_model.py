@@ -10,11 +10,12 @@ it goes through the HIP kernels of libgeoformer_hip.so.  The forward synchronise
 per batch (number of coarse matches after the second coarse matching, number of fine matches at the
 end); the RANSAC homography of GeoModule runs on the device, so nothing synchronises in between.
 """
-from typing import Dict, Optional
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn as nn
 
+from .. import ops
 from .backbone import build_backbone
 from .geo_config import default_cfg
 from .modules import (CoarseMatching, FineMatching2, FinePreprocess, GeoModule, LocalFeatureTransformer,
@@ -30,6 +31,18 @@ PRECISIONS = tuple(_PRECISIONS)   # the mode names, for interfaces that offer th
 
 
 _CONCURRENT_BACKBONES = [True]    # unequal-shape pairs: the two backbone calls on two streams (False: one after the other, for A/B)
+
+
+class ImageFeatures(NamedTuple):
+    """What the backbone makes of ONE image (GeoFormer.extract_features) - everything the matching path needs of it, so it can be kept
+    and matched against any number of other images (GeoFormer.match_features)."""
+    coarse: torch.Tensor             # [256, H/8, W/8] in backbone_dtype; may be a view into the storage of the batch it was extracted in
+    fine: torch.Tensor               # [128, H/2, W/2]
+    image_size: Tuple[int, int]      # (H, W) of the image
+
+    @property
+    def nbytes(self):
+        return self.coarse.numel() * self.coarse.element_size() + self.fine.numel() * self.fine.element_size()
 
 
 class GeoFormer(nn.Module):
@@ -182,6 +195,39 @@ class GeoFormer(nn.Module):
             (feat_c0, feat_f0), (feat_c1, feat_f1) = self._backbone_unequal(img0, img1)
         return self.forward_features(data, feat_c0, feat_f0, feat_c1, feat_f1)
 
+    # -- features once, matches many times.  The backbone's four maps depend on one image each; everything after them reads them
+    # through two kernels only (gf_pos_encode, gf_fine_gather), whose address-table forms read kept maps where they lie
+    def extract_features(self, images):
+        """images [K,1,H,W] on the device -> K ImageFeatures, from ONE backbone call (the 16-bit inference backbone in `backbone_dtype`
+        where the mode has one).  The maps are views into that call's two output tensors.  Eval mode only."""
+        if self.training:
+            raise RuntimeError('extract_features is an inference interface: call .eval() first (kept features carry no graph)')
+        if not images.is_cuda:
+            raise RuntimeError('geoformer_amd.GeoFormer runs on an MI355X (CUDA/HIP device) only; there is no CPU path')
+        feats_c, feats_f = self._backbone(images)
+        size = (int(images.shape[2]), int(images.shape[3]))
+        return [ImageFeatures(feats_c[k], feats_f[k], size) for k in range(images.shape[0])]
+
+    def match_features(self, feats0, feats1, data=None):
+        """Pair n = (feats0[n], feats1[n]), two lists of N ImageFeatures; a list may name one record N times (one query against N
+        candidates).  Runs `forward_features` on map batches (ops.MapBatch: the kept maps are read in place, nothing is copied into an
+        [N, ...] batch) and returns the usual `data` dict - the bits of `forward_features` on the same maps stacked.  Within a side
+        all records must agree in map shape, dtype and strides (ValueError).  Eval mode only; not captured into graphs
+        (`enable_graphs` concerns `forward`)."""
+        if self.training:
+            raise RuntimeError('match_features is an inference interface: call .eval() first')
+        feats0, feats1 = list(feats0), list(feats1)
+        if not feats0 or len(feats0) != len(feats1):
+            raise ValueError(f'match_features takes two lists of equal, non-zero length, got {len(feats0)} and {len(feats1)}')
+        for side in (feats0, feats1):
+            if any(f.image_size != side[0].image_size for f in side):
+                raise ValueError('match_features: the images of one side of a batch must have one size')
+        data = {} if data is None else data
+        data.update({'bs': torch.tensor(len(feats0)), 'hw0_i': torch.tensor(feats0[0].image_size),
+                     'hw1_i': torch.tensor(feats1[0].image_size)})
+        return self.forward_features(data, ops.MapBatch([f.coarse for f in feats0]), ops.MapBatch([f.fine for f in feats0]),
+                                     ops.MapBatch([f.coarse for f in feats1]), ops.MapBatch([f.fine for f in feats1]))
+
     def forward_static(self, data):
         """The part of the forward whose launches do not depend on data: backbone -> ... -> second coarse matching, with
         the match arrays at capacity and their counts on the device.  No host synchronisation: it can be captured into a
@@ -212,7 +258,8 @@ class GeoFormer(nn.Module):
         """Everything after the backbone.  Public so that parity tests and benchmarks can drive the
         matching path with given feature maps ([N,256,h,w] coarse, [N,128,4h,4w] fine).  The maps keep their own dtype
         (`backbone_dtype` when they come from the backbone): the two kernels that read them, gf_pos_encode (here and in
-        GeoModule.forward) and gf_fine_gather (FinePreprocess.forward), write `compute_dtype`; nothing else touches them."""
+        GeoModule.forward) and gf_fine_gather (FinePreprocess.forward), write `compute_dtype`; nothing else touches them - which is
+        why each of the four may also be an ops.MapBatch (`match_features`): only `.shape`, `.dtype` and `.device` are asked of them here."""
         dt = self.compute_dtype
         data.update({'hw0_c': torch.tensor(feat_c0.shape[2:]), 'hw1_c': torch.tensor(feat_c1.shape[2:]),
                      'hw0_f': torch.tensor(feat_f0.shape[2:]), 'hw1_f': torch.tensor(feat_f1.shape[2:])})

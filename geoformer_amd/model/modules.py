@@ -49,6 +49,7 @@ class PositionEncodingSine(nn.Module):
         return self._tables[key]
 
     def forward(self, x, out_dtype=None, out=None):
+        # x: the [N,C,H,W] map tensor, or an ops.MapBatch of N kept maps (passed through: ops.pos_encode reads them in place)
         _, _, h, w = x.shape
         return ops.pos_encode(x, self.table(h, w, x.device), out_dtype or x.dtype, out)
 
@@ -492,8 +493,11 @@ class GeoModule(nn.Module):
             mb = batch['m_bids']
             counts = torch.cat([torch.tensor([mb.numel()], device=dev), torch.bincount(mb, minlength=n)]).to(torch.int32)
             raw = {'mkpts0_c': batch['mkpts0_c'].contiguous(), 'mkpts1_c': batch['mkpts1_c'].contiguous(), 'counts': counts}
-        H0, W0 = batch['image0'].shape[2:]
-        H1, W1 = batch['image1'].shape[2:]
+        if 'image0' in batch:
+            H0, W0 = batch['image0'].shape[2:]
+            H1, W1 = batch['image1'].shape[2:]
+        else:                                      # kept features (GeoFormer.match_features) come without images: their sizes do
+            (H0, W0), (H1, W1) = (int(v) for v in batch['hw0_i']), (int(v) for v in batch['hw1_i'])
         scale = int(batch['hw0_i'][0]) // int(batch['hw0_c'][0])
         s0, s1 = batch.get('scale0'), batch.get('scale1')
         rs = ops.ransac_homography(raw['mkpts0_c'], raw['mkpts1_c'], raw['counts'], n, scale, s0, s1, self.ransac_thr,
@@ -517,7 +521,7 @@ class GeoModule(nn.Module):
     def forward(self, cnn_desc0, cnn_desc1, batch, desc_map0=None, desc_map1=None, dtype=None, desc_both=None):
         """cnn_desc0/1: raw backbone coarse maps [N,C,h,w]; position encoding is added here
         (geo_module.py:28-29) unless the caller passes the already encoded [N,L,C] maps (desc_both: the [2N,L,C] buffer
-        whose halves they are, if there is one)."""
+        whose halves they are, if there is one).  cnn_desc0/1 may be ops.MapBatch objects: only their shape and device are read here."""
         n = cnn_desc0.shape[0]
         hw0c, hw1c = tuple(cnn_desc0.shape[2:]), tuple(cnn_desc1.shape[2:])
         if desc_map0 is None:
@@ -564,6 +568,7 @@ class FinePreprocess(nn.Module):
         return w
 
     def forward(self, feat_f0, feat_f1, feat_c0, feat_c1, data: Dict[str, torch.Tensor]):
+        # feat_f0 / feat_f1: the fine map tensors, or two ops.MapBatch objects (kept maps, read in place by ops.fine_gather)
         W = self.W
         stride = int(data['hw0_f'][0]) // int(data['hw0_c'][0])
         data.update({'W': torch.tensor(W)})

@@ -139,15 +139,74 @@ def _i32p(t):
     return _p(t)
 
 
+class MapBatch:
+    """A batch of N feature maps that lie in SEPARATE allocations: a list of [C,H,W] device tensors of one shape, dtype, device and
+    stride triple (entries may repeat: one query map against N candidates), read where they lie by the address-table entries
+    gf_pos_encode_ptrs / gf_fine_gather_ptrs - `pos_encode` and `fine_gather` below take it in place of the [N,C,H,W] tensor.
+    Behaves like that tensor for `.shape`, `.dtype` and `.device`, and nothing more: the two ops are the only readers.
+    Raises ValueError when the maps differ in shape, dtype, device or strides."""
+
+    def __init__(self, maps):
+        maps = list(maps)
+        if not maps:
+            raise ValueError('MapBatch: no maps')
+        m0 = maps[0]
+        if m0.dim() != 3:
+            raise ValueError(f'MapBatch: maps are [C,H,W] tensors, got {tuple(m0.shape)}')
+        for m in maps[1:]:
+            if m.shape != m0.shape or m.dtype != m0.dtype or m.device != m0.device or m.stride() != m0.stride():
+                raise ValueError(f'MapBatch: the maps of a batch must agree in shape, dtype, device and strides: {tuple(m0.shape)} {m0.dtype} '
+                                 f'{m0.device} strides {m0.stride()} against {tuple(m.shape)} {m.dtype} {m.device} strides {m.stride()}')
+        self.maps = maps
+        self.shape = torch.Size((len(maps),) + tuple(m0.shape))
+        self.dtype, self.device = m0.dtype, m0.device
+        self.map_stride = tuple(m0.stride())                # (sc, sh, sw), elements
+        self.addresses = [m.data_ptr() for m in maps]
+        low = 256                                           # the largest power of two (bytes, capped) dividing every address
+        for a in self.addresses:
+            low = min(low, a & -a) if a else low
+        self.align = int(low)
+        self._tables = {}
+
+    def __len__(self):
+        return len(self.maps)
+
+    def size(self, dim=None):
+        return self.shape if dim is None else self.shape[dim]
+
+    def table(self):
+        """The N addresses as an int64 device tensor, for launches on the CURRENT stream.  No device synchronisation: the addresses are
+        written into a pinned host tensor and copied asynchronously on the current stream (torch's pinned-memory allocator holds the
+        host block back until that copy has run).  Kept per stream by this object, so it lives as long as the batch does and at least
+        until the launches that read it have been enqueued; freed afterwards, the caching allocator's stream order keeps the block from
+        being handed out to work that runs before them."""
+        key = _stream_handle(self.device)
+        t = self._tables.get(key)
+        if t is None:
+            host = torch.tensor(self.addresses, dtype=torch.int64).pin_memory()
+            with torch.cuda.device(self.device):
+                t = self._tables[key] = host.to(self.device, non_blocking=True)
+        return t
+
+
 def pos_encode(x, pe_hwc, out_dtype, out=None):
     """a1.  x [N,C,H,W] (any strides; fp32, fp16 or bf16), pe_hwc fp32 [H,W,C] on the device -> [N, H*W, C] of out_dtype (into `out`
-    if given).  Any input / output dtype pair, bf16 -> fp16 and fp16 -> bf16 included: bit-equal to (x.float() + pe).to(out_dtype)."""
-    _need_cuda(x, pe_hwc)
+    if given).  Any input / output dtype pair, bf16 -> fp16 and fp16 -> bf16 included: bit-equal to (x.float() + pe).to(out_dtype).
+    x may be a MapBatch (N maps in separate allocations, read in place through gf_pos_encode_ptrs): the bits of the tensor path on
+    torch.stack of the maps."""
+    _need_cuda(pe_hwc)
     N, C, H, W = x.shape
     if out is None:
         out = torch.empty(N, H * W, C, dtype=out_dtype, device=x.device)
     elif out.shape != (N, H * W, C) or out.dtype != out_dtype or not out.is_contiguous():
         raise ValueError('out must be a contiguous [N, H*W, C] tensor of out_dtype')
+    if isinstance(x, MapBatch):
+        _need_cuda(*x.maps)
+        sc, sh, sw = x.map_stride
+        check(_lib.lib().gf_pos_encode_ptrs(_p(x.table()), _dt(x), sc, sh, sw, x.align, _p(pe_hwc), _p(out), _DTYPES[out_dtype], N, C, H, W,
+                                            _stream()), 'gf_pos_encode_ptrs')
+        return out
+    _need_cuda(x)
     sn, sc, sh, sw = x.stride()
     check(_lib.lib().gf_pos_encode(_p(x), _dt(x), sn, sc, sh, sw, _p(pe_hwc), _p(out), _DTYPES[out_dtype], N, C, H, W,
                                    _stream()), 'gf_pos_encode')
@@ -578,19 +637,37 @@ def window_cross_attention_backward(q, kmap, vmap, dout, win, nhead=4):
 def fine_gather(feat_f0, feat_f1, feat_c0, feat_c1, b_ids, i_ids, j_ids, w0c, w1c, stride, window, out_dtype):
     """K7.  feat_f* [N,Cf,H,W] any strides, both of one dtype (fp32, fp16 or bf16; it need not be out_dtype); feat_c* [N,L,CC]
     contiguous of out_dtype; ids int64 [M] (M > 0) -> (win [2M, W*W, Cf], ccat [2M, CC]), both of out_dtype.  The window values
-    are feat.float().to(out_dtype) bit for bit (bf16 maps -> fp16 windows: the 'bf16_fp16' mode; no clamp: beyond fp16's range -> inf)."""
-    _need_cuda(feat_f0, feat_f1, feat_c0, feat_c1, b_ids)
+    are feat.float().to(out_dtype) bit for bit (bf16 maps -> fp16 windows: the 'bf16_fp16' mode; no clamp: beyond fp16's range -> inf).
+    feat_f0 / feat_f1 may be MapBatches (both, or neither): the maps are read in place through gf_fine_gather_ptrs, same bits."""
+    tables = isinstance(feat_f0, MapBatch)
+    if tables != isinstance(feat_f1, MapBatch):
+        raise TypeError('fine_gather: feat_f0 and feat_f1 must both be tensors or both be MapBatches')
+    if tables:
+        _need_cuda(*feat_f0.maps, *feat_f1.maps, feat_c0, feat_c1, b_ids)
+        if len(feat_f0) != len(feat_f1):
+            raise ValueError(f'fine_gather: {len(feat_f0)} maps on side 0, {len(feat_f1)} on side 1')
+    else:
+        _need_cuda(feat_f0, feat_f1, feat_c0, feat_c1, b_ids)
     M = b_ids.shape[0]
     Cf = feat_f0.shape[1]
     CC = feat_c0.shape[-1]
     dev = feat_f0.device
     win = torch.empty(2 * M, window * window, Cf, dtype=out_dtype, device=dev)
     ccat = torch.empty(2 * M, CC, dtype=out_dtype, device=dev)
-    s0 = (ctypes.c_long * 4)(*feat_f0.stride())
-    s1 = (ctypes.c_long * 4)(*feat_f1.stride())
     fc0, fc1 = _contig(feat_c0), _contig(feat_c1)
     if fc0.dtype != out_dtype or fc1.dtype != out_dtype or feat_f0.dtype != feat_f1.dtype:
         raise TypeError('fine_gather: coarse features must already be in out_dtype; fine maps must share a dtype')
+    if tables:
+        s0 = (ctypes.c_long * 3)(*feat_f0.map_stride)
+        s1 = (ctypes.c_long * 3)(*feat_f1.map_stride)
+        check(_lib.lib().gf_fine_gather_ptrs(_p(feat_f0.table()), _p(feat_f1.table()), len(feat_f0), _dt(feat_f0), min(feat_f0.align, feat_f1.align),
+                                             ctypes.cast(s0, ctypes.c_void_p), ctypes.cast(s1, ctypes.c_void_p), feat_f0.shape[2],
+                                             feat_f0.shape[3], feat_f1.shape[2], feat_f1.shape[3], Cf, _p(fc0), _p(fc1), _DTYPES[out_dtype],
+                                             fc0.shape[1], fc1.shape[1], CC, _p(_contig(b_ids)), _p(_contig(i_ids)), _p(_contig(j_ids)), M,
+                                             int(w0c), int(w1c), int(stride), int(window), _p(win), _p(ccat), _stream()), 'gf_fine_gather_ptrs')
+        return win, ccat
+    s0 = (ctypes.c_long * 4)(*feat_f0.stride())
+    s1 = (ctypes.c_long * 4)(*feat_f1.stride())
     check(_lib.lib().gf_fine_gather(_p(feat_f0), _p(feat_f1), _dt(feat_f0), ctypes.cast(s0, ctypes.c_void_p),
                                     ctypes.cast(s1, ctypes.c_void_p), feat_f0.shape[2], feat_f0.shape[3], feat_f1.shape[2],
                                     feat_f1.shape[3], Cf, _p(fc0), _p(fc1), _DTYPES[out_dtype], fc0.shape[1], fc1.shape[1],

@@ -582,6 +582,26 @@ int gf_image_warp_resize(const void* src, int channels, int hs, int ws, long lon
                          int warp_h, int warp_w, void* dst, int dst_kind, int ht, int wt, const float* brightness_contrast,
                          void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Address-table siblings of gf_pos_encode and gf_fine_gather: the maps of the N samples lie in SEPARATE allocations (feature maps
+ * kept per image and matched many times) and are read where they lie - no copy into an [N, ...] batch first.  The only difference
+ * from the sibling: sample n starts at table[n] (a table of N addresses in DEVICE memory, entries may repeat) instead of x + n * sn.
+ * Same kernels (templated on how the base is obtained), same arithmetic, same output bits as the sibling on torch.stack of the maps.
+ *   *_align  the largest power of two, in bytes, that divides every table entry (the caller built the table on the host and knows;
+ *            any smaller power of two is valid and only selects a slower form): the 8-channel vector form of the position encoding
+ *            needs 32, the one-wave-per-window form of the gather 16 - the alignment conditions of the siblings, for every entry.
+ *   strides  element strides of ONE map viewed as [C, H, W] (sc, sh, sw), common to all samples; gf_fine_gather_ptrs takes them as
+ *            two arrays of 3.  N <= 65535 for gf_pos_encode_ptrs.  Everything else as in the sibling; feat_c0 / feat_c1 stay plain tensors.
+ *   The table is read by the launch: it must stay valid (and unchanged) until the launch has run - stream order suffices.
+ * ------------------------------------------------------------------------------------------ */
+int gf_pos_encode_ptrs(const void* const* x_table, int x_dtype, long sc, long sh, long sw, int x_align, const float* pe,
+                       void* out, int out_dtype, int N, int C, int H, int W, void* stream);
+int gf_fine_gather_ptrs(const void* const* f0_table, const void* const* f1_table, int N, int feat_dtype, int feat_align,
+                        const long* strides0, const long* strides1, int H0, int W0, int H1, int W1, int C,
+                        const void* feat_c0, const void* feat_c1, int dtype, int L, int S, int CC, const int64_t* b_ids,
+                        const int64_t* i_ids, const int64_t* j_ids, int M, int w0c, int w1c, int stride, int window,
+                        void* win_out, void* ccat_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
