@@ -4,6 +4,7 @@
 //                   (b_ids, i_ids / j_ids) (model/loftr_src/loftr/loftr_module/fine_preprocess.py:41-56),
 //                   without materialising the [N, 25*C, L] unfold: each match reads only its own 5x5
 //                   window; plus the gather of the two coarse feature rows that feed down_proj (:61).
+//                   gf_fine_gather_ptrs: the N maps of a side in separate allocations; gf_fine_gather_ragged: of unequal extents too.
 //   gf_fine_match   K8 (a14/a15): FineMatching2.forward + get_fine_match (model/fine_matching2.py:21-126):
 //                   25x25 dual-softmax per match, global arg-max, threshold, ordered compaction and the
 //                   fine keypoint arithmetic.
@@ -113,6 +114,88 @@ __global__ __launch_bounds__(256) void fine_gather_rows(FgArgs a) {
         v4u v = zero;
         if (y >= 0 && y < Hf && x >= 0 && x < Wf) v = fg_convert8<TF, T>(*reinterpret_cast<const v4u*>(f + (TBL ? 0 : b * sn) + y * sh + x * sw + c8));
         *reinterpret_cast<v4u*>(out + (size_t)k * a.C + c8) = v;
+    }
+    const T* cf = (const T*)(side ? a.c1 : a.c0) + ((size_t)b * (side ? a.S : a.L) + cell) * a.CC;
+    T* co = (T*)a.ccat + (size_t)u * a.CC;
+    for (int c8 = lane * 8; c8 < a.CC; c8 += 512) *reinterpret_cast<v4u*>(co + c8) = *reinterpret_cast<const v4u*>(cf + c8);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Ragged forms (gf_fine_gather_ragged): the fine maps of a side differ in extent and lie at the top left of a common canvas.  The table
+// entry of sample b is a gf_map_record (base, strides, extent) instead of a bare address, so Hf, Wf and the strides are per sample; a tap
+// outside the sample's OWN extent is zero like F.unfold's padding - also where memory continues behind the map: nothing outside
+// [0, h) x [0, w) is loaded.  b is uniform per workgroup / wave as in the TBL forms: the record is a few scalar loads in front of the loop.
+struct FgRagArgs {
+    const gf_map_record* t0;   // [N] per side, device memory
+    const gf_map_record* t1;
+    int C;
+    const void* c0;            // coarse (geo) features [N, L, CC], [N, S, CC]
+    const void* c1;
+    int L, S, CC;
+    const int64_t* b_ids;
+    const int64_t* i_ids;
+    const int64_t* j_ids;
+    int M, w0c, w1c, stride, W;   // w0c / w1c: the CANVAS width in coarse cells
+    void* win;                 // [2M][W*W][C]
+    void* ccat;                // [2M][CC]
+};
+
+// one workgroup per (match, side): thread c < C copies channel c of the window positions
+template <typename TF, typename T>
+__global__ __launch_bounds__(256) void fine_gather_ragged(FgRagArgs a) {
+    const int m = blockIdx.x, side = blockIdx.y, t = threadIdx.x;
+    const int b = (int)a.b_ids[m];
+    const int cell = (int)(side ? a.j_ids[m] : a.i_ids[m]);
+    const int wc = side ? a.w1c : a.w0c;
+    const gf_map_record r = (side ? a.t1 : a.t0)[b];              // b = b_ids[blockIdx.x]: uniform
+    const TF* f = (const TF*)r.base;
+    const int cy = (cell / wc) * a.stride - a.W / 2, cx = (cell % wc) * a.stride - a.W / 2;
+    T* out = (T*)a.win + ((size_t)side * a.M + m) * a.W * a.W * a.C;
+    if (t < a.C) {
+        for (int k = 0; k < a.W * a.W; ++k) {
+            const int y = cy + k / a.W, x = cx + k % a.W;
+            float v = 0.f;                                        // F.unfold's padding, and the canvas beyond the sample's extent
+            if (y >= 0 && y < r.h && x >= 0 && x < r.w) v = gf_to_float(f[t * r.sc + y * r.sh + x * r.sw]);
+            out[(size_t)k * a.C + t] = gf_from_float<T>(v);
+        }
+    }
+    const T* cf = (const T*)(side ? a.c1 : a.c0) + ((size_t)b * (side ? a.S : a.L) + cell) * a.CC;
+    T* co = (T*)a.ccat + ((size_t)side * a.M + m) * a.CC;
+    for (int c = t; c < a.CC; c += blockDim.x) co[c] = cf[c];
+}
+
+// the 16-bit form: one wave per (match, side), 16-byte pieces (fine_gather_rows above).  Whether a sample's map can be read in pieces
+// (channels-last, row and pixel strides multiples of 8 elements) is known from its record only: a wave whose sample cannot takes the
+// element loop instead - same values, a uniform branch.
+template <typename TF, typename T>
+__global__ __launch_bounds__(256) void fine_gather_rows_ragged(FgRagArgs a) {
+    static_assert(sizeof(TF) == 2 && sizeof(T) == 2, "16-byte pieces of 8 elements on both sides");
+    const int lane = threadIdx.x & 63, u = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+    if (u >= 2 * a.M) return;
+    const int side = u >= a.M, m = side ? u - a.M : u;
+    const int b = (int)a.b_ids[m];
+    const int cell = (int)(side ? a.j_ids[m] : a.i_ids[m]);
+    const int wc = side ? a.w1c : a.w0c;
+    const gf_map_record r = (side ? a.t1 : a.t0)[b];
+    const TF* f = (const TF*)r.base;
+    const int cy = (cell / wc) * a.stride - a.W / 2, cx = (cell % wc) * a.stride - a.W / 2;
+    T* out = (T*)a.win + (size_t)u * a.W * a.W * a.C;
+    if (r.sc == 1 && r.sh % 8 == 0 && r.sw % 8 == 0) {
+        const int ppp = a.C / 8, pieces = a.W * a.W * ppp;              // 16-byte pieces per position / per window
+        const v4u zero{0u, 0u, 0u, 0u};
+        for (int e = lane; e < pieces; e += 64) {
+            const int k = e / ppp, c8 = (e - k * ppp) * 8, y = cy + k / a.W, x = cx + k % a.W;
+            v4u v = zero;
+            if (y >= 0 && y < r.h && x >= 0 && x < r.w) v = fg_convert8<TF, T>(*reinterpret_cast<const v4u*>(f + y * r.sh + x * r.sw + c8));
+            *reinterpret_cast<v4u*>(out + (size_t)k * a.C + c8) = v;
+        }
+    } else {
+        for (int e = lane; e < a.W * a.W * a.C; e += 64) {
+            const int k = e / a.C, c = e - k * a.C, y = cy + k / a.W, x = cx + k % a.W;
+            float v = 0.f;
+            if (y >= 0 && y < r.h && x >= 0 && x < r.w) v = gf_to_float(f[c * r.sc + y * r.sh + x * r.sw]);
+            out[e] = gf_from_float<T>(v);
+        }
     }
     const T* cf = (const T*)(side ? a.c1 : a.c0) + ((size_t)b * (side ? a.S : a.L) + cell) * a.CC;
     T* co = (T*)a.ccat + (size_t)u * a.CC;
@@ -377,6 +460,28 @@ int fg_dispatch(int feat_dtype, int dtype, const FgArgs& a, hipStream_t st, unsi
     return fg_launch_to<gf_bf16, TBL>(dtype, a, st, feat_align);
 }
 
+template <typename TF, typename T>
+int fg_ragged_launch(const FgRagArgs& a, hipStream_t st, unsigned feat_align) {
+    if constexpr (sizeof(TF) == 2 && sizeof(T) == 2) {
+        const bool rows16 = feat_align % 16 == 0 && a.C % 8 == 0 && a.CC % 8 == 0 && (uintptr_t)a.c0 % 16 == 0 && (uintptr_t)a.c1 % 16 == 0 &&
+                            (uintptr_t)a.win % 16 == 0 && (uintptr_t)a.ccat % 16 == 0;
+        if (rows16) {
+            fine_gather_rows_ragged<TF, T><<<(2 * a.M + 3) / 4, 256, 0, st>>>(a);
+            GF_CHECK_LAUNCH();
+            return GF_OK;
+        }
+    }
+    fine_gather_ragged<TF, T><<<dim3(a.M, 2), 256, 0, st>>>(a);
+    GF_CHECK_LAUNCH();
+    return GF_OK;
+}
+
+template <typename TF>
+int fg_ragged_to(int dtype, const FgRagArgs& a, hipStream_t st, unsigned feat_align) {
+    return dtype == GF_F32 ? fg_ragged_launch<TF, float>(a, st, feat_align)
+                           : dtype == GF_F16 ? fg_ragged_launch<TF, _Float16>(a, st, feat_align) : fg_ragged_launch<TF, gf_bf16>(a, st, feat_align);
+}
+
 }   // namespace
 
 extern "C" int gf_fine_gather(const void* feat_f0, const void* feat_f1, int feat_dtype, const long* strides0,
@@ -409,6 +514,24 @@ extern "C" int gf_fine_gather_ptrs(const void* const* f0_table, const void* cons
              H0, W0, H1, W1, C, feat_c0, feat_c1, L, S, CC, b_ids, i_ids, j_ids, M, w0c, w1c, stride, window,
              win_out, ccat_out};
     return fg_dispatch<true>(feat_dtype, dtype, a, (hipStream_t)stream, (unsigned)feat_align);
+}
+
+extern "C" int gf_fine_gather_ragged(const gf_map_record* f0_table, const gf_map_record* f1_table, int N, int feat_dtype, int feat_align, int C,
+                                     const void* feat_c0, const void* feat_c1, int dtype, int L, int S, int CC, const int64_t* b_ids,
+                                     const int64_t* i_ids, const int64_t* j_ids, int M, int w0c, int w1c, int stride, int window,
+                                     void* win_out, void* ccat_out, void* stream) {
+    GF_CHECK_ARG(f0_table && f1_table && feat_c0 && feat_c1 && b_ids && i_ids && j_ids && win_out && ccat_out, "null pointer");
+    GF_CHECK_ARG(N > 0, "empty table");
+    GF_CHECK_ARG(N <= 65535, "at most 65535 table entries");
+    GF_CHECK_ARG(M > 0, "M must be > 0 (the M == 0 early return of fine_preprocess.py:35-38 is the caller's)");
+    GF_CHECK_ARG(C > 0 && C <= 256 && window > 0 && stride > 0 && w0c > 0 && w1c > 0, "bad sizes");
+    GF_CHECK_ARG(feat_align > 0 && (feat_align & (feat_align - 1)) == 0, "feat_align must be a power of two");
+    GF_CHECK_ARG(feat_dtype >= GF_F32 && feat_dtype <= GF_BF16 && dtype >= GF_F32 && dtype <= GF_BF16, "bad dtype");
+    FgRagArgs a{f0_table, f1_table, C, feat_c0, feat_c1, L, S, CC, b_ids, i_ids, j_ids, M, w0c, w1c, stride, window, win_out, ccat_out};
+    hipStream_t st = (hipStream_t)stream;
+    if (feat_dtype == GF_F32) return fg_ragged_to<float>(dtype, a, st, (unsigned)feat_align);
+    if (feat_dtype == GF_F16) return fg_ragged_to<_Float16>(dtype, a, st, (unsigned)feat_align);
+    return fg_ragged_to<gf_bf16>(dtype, a, st, (unsigned)feat_align);
 }
 
 extern "C" size_t gf_fine_match_workspace_bytes(int M) {

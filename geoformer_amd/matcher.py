@@ -267,6 +267,42 @@ def group_pairs(shapes, batch):
     return [idx[s:s + batch] for idx in groups.values() for s in range(0, len(idx), batch)]
 
 
+# match_many(pad=True): see group_pairs_padded.  The best of {1.1, 1.25, 1.5, 2} in profiles/padded_batch.txt (tools/padded_batch_probe.py: 120 pairs
+# over 8 sizes, 1420.7 pairs/s against 1412.0 .. 1414.3 for the others and 1270.0 unpadded) - a lead inside that run's spread, and the candidate that
+# changes a pair's matches least
+DEFAULT_PAD_WASTE = 1.1
+
+
+def group_pairs_padded(shapes, batch, max_waste):
+    """shapes[k] = ((h0, w0), (h1, w1)): pair k's two map (or image) shapes.  -> list of index lists for padded batches: every index
+    once, at most `batch` per list, a list's indices in input order.  Pairs are ordered by the area of their two shapes (ties: input
+    order) and batches filled greedily in that order; a batch is closed when it is full, or when adding the next pair would push, on
+    either side, count x canvas area (the canvas: the per-axis maximum over the batch) above max_waste x the sum of the pairs' own
+    areas - the matching path's work grows with the canvas, so max_waste bounds the work spent on padding.  max_waste = 1 batches
+    equal shapes only; one shape throughout gives group_pairs' batches."""
+    if batch < 1:
+        raise ValueError('batch must be >= 1')
+    if not max_waste >= 1:
+        raise ValueError('max_waste must be >= 1 (canvas area over own area)')
+    shapes = [tuple((int(h), int(w)) for h, w in sh) for sh in shapes]
+    order = sorted(range(len(shapes)), key=lambda k: (sum(h * w for h, w in shapes[k]), k))
+    out, cur = [], []
+    canvas, own = [(0, 0), (0, 0)], [0, 0]
+    for k in order:
+        new_canvas = [(max(c[0], s[0]), max(c[1], s[1])) for c, s in zip(canvas, shapes[k])]
+        new_own = [o + s[0] * s[1] for o, s in zip(own, shapes[k])]
+        fits = len(cur) < batch and all((len(cur) + 1) * c[0] * c[1] <= max_waste * o for c, o in zip(new_canvas, new_own))
+        if cur and not fits:
+            out.append(sorted(cur))
+            cur = []
+            new_canvas, new_own = list(shapes[k]), [s[0] * s[1] for s in shapes[k]]
+        cur.append(k)
+        canvas, own = new_canvas, new_own
+    if cur:
+        out.append(sorted(cur))
+    return out
+
+
 def read_pair_list(list_path):
     """Two image paths per line (whitespace separated; blank lines and lines starting with '#' are skipped); a relative path is
     relative to the directory of the list file."""
@@ -397,11 +433,15 @@ class GeoFormerMatcher:
         """match_pairs with both images going through the store (an image that recurs is extracted once)."""
         return self.match_features(self.extract(im1_path, slot=0), self.extract(im2_path, slot=1))
 
-    def match_many(self, pairs, batch=8):
+    def match_many(self, pairs, batch=8, pad=False, max_waste=None):
         """[(path0, path1), ...] -> one match_pairs-style tuple per pair, in the order of `pairs`.  Pairs are grouped by their two
         resized shapes and run `batch` at a time through GeoFormer.match_features; every image is extracted once (once per stay in the
         store, under a byte budget).  A pair's numbers are those of the model on ITS BATCH - as with any batched `forward`, the device
-        RANSAC draws its samples per position in the batch - so they equal match_pairs' exactly for batches of one pair."""
+        RANSAC draws its samples per position in the batch - so they equal match_pairs' exactly for batches of one pair.
+        pad=True: pairs of UNEQUAL shapes share a batch (group_pairs_padded with max_waste, default DEFAULT_PAD_WASTE): the kept maps
+        are matched on a common canvas with padding masks (GeoFormer.match_features(pad=True)); the backbone never sees padding and
+        each record's own resize ratios still scale its keypoints (the maps share the canvas's origin).  A list of one shape gives
+        the bits of pad=False."""
         pairs = [tuple(p) for p in pairs]
         shape = {}
         for p in pairs:
@@ -409,11 +449,14 @@ class GeoFormerMatcher:
                 if path not in shape:
                     shape[path] = self.resized_shape(path)
         results = [None] * len(pairs)
-        for idx in group_pairs([(shape[a], shape[b]) for a, b in pairs], batch):
+        pair_shapes = [(shape[a], shape[b]) for a, b in pairs]
+        groups = (group_pairs_padded(pair_shapes, batch, DEFAULT_PAD_WASTE if max_waste is None else max_waste) if pad
+                  else group_pairs(pair_shapes, batch))
+        for idx in groups:
             recs0 = [self.extract(pairs[k][0], slot=0) for k in idx]       # held here: eviction cannot free a map of the batch in flight
             recs1 = [self.extract(pairs[k][1], slot=1) for k in idx]
             with torch.no_grad():
-                data = self.model.match_features([r.features for r in recs0], [r.features for r in recs1])
+                data = self.model.match_features([r.features for r in recs0], [r.features for r in recs1], pad=pad)
             for k, res in zip(idx, self._results(data, recs0, recs1)):
                 results[k] = res
         return results
@@ -548,7 +591,7 @@ def eval_hpatches(matcher, data_root, ransac_thres=3, thres=(1, 3, 5, 10), scale
 # command line: the counterparts of `python inference.py` and `python eval_Hpatches.py`
 #   python -m geoformer_amd.matcher match im1 im2 [--ckpt saved_ckpt/geoformer.ckpt] [--out matches.npz] [--preprocess device]
 #   python -m geoformer_amd.matcher hpatches /path/to/hpatches-sequences-release [--ckpt ...] [--preprocess device] [--reuse-features]
-#   python -m geoformer_amd.matcher pairs LIST | --all-pairs DIR  [--out DIR] [--batch B] [--cache-gb G]      (no reference counterpart)
+#   python -m geoformer_amd.matcher pairs LIST | --all-pairs DIR  [--out DIR] [--batch B] [--cache-gb G] [--pad [--pad-waste R]]   (no reference counterpart)
 # ---------------------------------------------------------------------------------------------
 def build_parser():
     """Defaults follow the reference per sub-command: `match` = inference.py:107 (imsize 640, matches scaled back to the
@@ -580,6 +623,10 @@ def build_parser():
     q.add_argument('--batch', type=int, default=8, help='pairs of equal shapes matched per model call')
     q.add_argument('--imsize', type=int, default=640)
     q.add_argument('--no-match-upscale', action='store_true')
+    q.add_argument('--pad', action='store_true',
+                   help='let pairs of unequal shapes share a batch: kept feature maps on a common canvas with padding masks')
+    q.add_argument('--pad-waste', type=float, default=None, metavar='R',
+                   help=f'with --pad: close a batch before its canvas area exceeds R times its pairs\' own area (default {DEFAULT_PAD_WASTE})')
     for p in (h, q):
         p.add_argument('--cache-gb', type=float, default=None,
                        help='byte budget of the feature store in GB: least recently used images are dropped and extracted again when '
@@ -616,7 +663,7 @@ def main(argv=None):
                                cache_bytes=None if cache_gb is None else int(cache_gb * 2 ** 30))
     if args.cmd == 'pairs':
         pairs = read_pair_list(args.list) if args.list is not None else all_pairs(args.all_pairs)
-        results = matcher.match_many(pairs, batch=args.batch)
+        results = matcher.match_many(pairs, batch=args.batch, pad=args.pad, max_waste=args.pad_waste)
         if args.out:
             os.makedirs(args.out, exist_ok=True)
         for k, ((p0, p1), res) in enumerate(zip(pairs, results)):

@@ -208,25 +208,55 @@ class GeoFormer(nn.Module):
         size = (int(images.shape[2]), int(images.shape[3]))
         return [ImageFeatures(feats_c[k], feats_f[k], size) for k in range(images.shape[0])]
 
-    def match_features(self, feats0, feats1, data=None):
+    def match_features(self, feats0, feats1, data=None, pad=False):
         """Pair n = (feats0[n], feats1[n]), two lists of N ImageFeatures; a list may name one record N times (one query against N
         candidates).  Runs `forward_features` on map batches (ops.MapBatch: the kept maps are read in place, nothing is copied into an
         [N, ...] batch) and returns the usual `data` dict - the bits of `forward_features` on the same maps stacked.  Within a side
         all records must agree in map shape, dtype and strides (ValueError).  Eval mode only; not captured into graphs
-        (`enable_graphs` concerns `forward`)."""
+        (`enable_graphs` concerns `forward`).
+        pad=True: a side whose records disagree in image size is matched as ONE padded batch (ops.RaggedMapBatch: the maps stay where
+        they lie, anchored at the top left of a canvas of the per-axis maximum; nothing runs through the backbone again).  hw*_i is then
+        the canvas's image size and data['mask0'] / ['mask1'] are the bool [N,hc,wc] padding masks, written by the position-encoding
+        launch (all true for a side of one size) - the bits of `forward_features` on the maps zero-padded and stacked with those masks.
+        Keypoints are in each image's own resized coordinates (the maps share the canvas's origin).  Two uniform sides take the path
+        above, without masks.  As in every masked batch, (padded cell, padded cell) entries of a sample with padding on BOTH sides have
+        conf = 1 / (L S), the reference's finite -1e9 fill: a coarse threshold of exactly 0 lets them through, any real one does not."""
         if self.training:
             raise RuntimeError('match_features is an inference interface: call .eval() first')
         feats0, feats1 = list(feats0), list(feats1)
         if not feats0 or len(feats0) != len(feats1):
             raise ValueError(f'match_features takes two lists of equal, non-zero length, got {len(feats0)} and {len(feats1)}')
-        for side in (feats0, feats1):
-            if any(f.image_size != side[0].image_size for f in side):
-                raise ValueError('match_features: the images of one side of a batch must have one size')
+        mixed = [any(f.image_size != side[0].image_size for f in side) for side in (feats0, feats1)]
+        if any(mixed) and not pad:
+            raise ValueError('match_features: the images of one side of a batch must have one size')
         data = {} if data is None else data
-        data.update({'bs': torch.tensor(len(feats0)), 'hw0_i': torch.tensor(feats0[0].image_size),
-                     'hw1_i': torch.tensor(feats1[0].image_size)})
-        return self.forward_features(data, ops.MapBatch([f.coarse for f in feats0]), ops.MapBatch([f.fine for f in feats0]),
-                                     ops.MapBatch([f.coarse for f in feats1]), ops.MapBatch([f.fine for f in feats1]))
+        if not any(mixed):
+            data.update({'bs': torch.tensor(len(feats0)), 'hw0_i': torch.tensor(feats0[0].image_size),
+                         'hw1_i': torch.tensor(feats1[0].image_size)})
+            return self.forward_features(data, ops.MapBatch([f.coarse for f in feats0]), ops.MapBatch([f.fine for f in feats0]),
+                                         ops.MapBatch([f.coarse for f in feats1]), ops.MapBatch([f.fine for f in feats1]))
+        n, dev = len(feats0), feats0[0].coarse.device
+        batches, masks, mask_outs = [], [], []
+        for k, side in enumerate((feats0, feats1)):
+            hi, wi = max(f.image_size[0] for f in side), max(f.image_size[1] for f in side)
+            data[f'hw{k}_i'] = torch.tensor((hi, wi))
+            if mixed[k]:
+                hc, wc = max(f.coarse.shape[1] for f in side), max(f.coarse.shape[2] for f in side)
+                coarse = ops.RaggedMapBatch([f.coarse for f in side])
+                # the fine canvas is the coarse canvas at the fine level's stride, whatever the fine maps' own maxima are
+                ratio = side[0].fine.shape[1] // side[0].coarse.shape[1]
+                fine = ops.RaggedMapBatch([f.fine for f in side], canvas=(hc * ratio, wc * ratio))
+                mask = torch.empty(n, hc, wc, dtype=torch.bool, device=dev)        # written by this side's position-encoding launch
+                mask_outs.append(mask)
+            else:
+                # a ragged batch of equal extents: fine_gather takes two batches of ONE kind; nothing is padding, nothing to write
+                coarse, fine = ops.RaggedMapBatch([f.coarse for f in side]), ops.RaggedMapBatch([f.fine for f in side])
+                mask = torch.ones(n, *coarse.shape[2:], dtype=torch.bool, device=dev)
+                mask_outs.append(None)
+            batches += [coarse, fine]
+            masks.append(mask)
+        data.update({'bs': torch.tensor(n), 'mask0': masks[0], 'mask1': masks[1], '_pe_mask_out': tuple(mask_outs)})
+        return self.forward_features(data, *batches)
 
     def forward_static(self, data):
         """The part of the forward whose launches do not depend on data: backbone -> ... -> second coarse matching, with
@@ -268,16 +298,17 @@ class GeoFormer(nn.Module):
                          'hw1_i': torch.tensor(data['image1'].shape[2:])})
         # 2. position encoding + flatten, coarse LoFTR transformer
         pe_both = None
+        mo0, mo1 = data.pop('_pe_mask_out', (None, None))      # match_features(pad=True): the padding masks in data are filled by these launches
         if feat_c0.shape == feat_c1.shape:
             # both position-encoded maps in ONE [2N, L, C] buffer: the two transformers batch the images of a pair and would
             # otherwise concatenate them (52 MB per 8 pairs, twice per step); nothing writes into it afterwards
             n, c, h, w = feat_c0.shape
             pe_both = torch.empty(2 * n, h * w, c, dtype=dt, device=feat_c0.device)
-            pe0 = self.pos_encoding(feat_c0, dt, out=pe_both[:n])
-            pe1 = self.pos_encoding(feat_c1, dt, out=pe_both[n:])
+            pe0 = self.pos_encoding(feat_c0, dt, out=pe_both[:n], mask_out=mo0)
+            pe1 = self.pos_encoding(feat_c1, dt, out=pe_both[n:], mask_out=mo1)
         else:
-            pe0 = self.pos_encoding(feat_c0, dt)
-            pe1 = self.pos_encoding(feat_c1, dt)
+            pe0 = self.pos_encoding(feat_c0, dt, mask_out=mo0)
+            pe1 = self.pos_encoding(feat_c1, dt, mask_out=mo1)
         mask_c0 = mask_c1 = None
         if 'mask0' in data:
             mask_c0, mask_c1 = data['mask0'].flatten(-2), data['mask1'].flatten(-2)

@@ -48,10 +48,11 @@ class PositionEncodingSine(nn.Module):
             self._tables[key] = pe.permute(1, 2, 0).contiguous().to(device)
         return self._tables[key]
 
-    def forward(self, x, out_dtype=None, out=None):
-        # x: the [N,C,H,W] map tensor, or an ops.MapBatch of N kept maps (passed through: ops.pos_encode reads them in place)
+    def forward(self, x, out_dtype=None, out=None, mask_out=None):
+        # x: the [N,C,H,W] map tensor, or an ops.MapBatch / ops.RaggedMapBatch of N kept maps (passed through: ops.pos_encode reads them in
+        # place; a ragged batch reports its canvas as h, w and can have its padding mask written by the same launch)
         _, _, h, w = x.shape
-        return ops.pos_encode(x, self.table(h, w, x.device), out_dtype or x.dtype, out)
+        return ops.pos_encode(x, self.table(h, w, x.device), out_dtype or x.dtype, out, mask_out)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -521,7 +522,8 @@ class GeoModule(nn.Module):
     def forward(self, cnn_desc0, cnn_desc1, batch, desc_map0=None, desc_map1=None, dtype=None, desc_both=None):
         """cnn_desc0/1: raw backbone coarse maps [N,C,h,w]; position encoding is added here
         (geo_module.py:28-29) unless the caller passes the already encoded [N,L,C] maps (desc_both: the [2N,L,C] buffer
-        whose halves they are, if there is one).  cnn_desc0/1 may be ops.MapBatch objects: only their shape and device are read here."""
+        whose halves they are, if there is one).  cnn_desc0/1 may be ops.MapBatch or ops.RaggedMapBatch objects: only their shape and device are
+        read here (and pos_encoding takes either)."""
         n = cnn_desc0.shape[0]
         hw0c, hw1c = tuple(cnn_desc0.shape[2:]), tuple(cnn_desc1.shape[2:])
         if desc_map0 is None:
@@ -568,7 +570,7 @@ class FinePreprocess(nn.Module):
         return w
 
     def forward(self, feat_f0, feat_f1, feat_c0, feat_c1, data: Dict[str, torch.Tensor]):
-        # feat_f0 / feat_f1: the fine map tensors, or two ops.MapBatch objects (kept maps, read in place by ops.fine_gather)
+        # feat_f0 / feat_f1: the fine map tensors, or two ops.MapBatch / two ops.RaggedMapBatch objects (kept maps, read in place by ops.fine_gather)
         W = self.W
         stride = int(data['hw0_f'][0]) // int(data['hw0_c'][0])
         data.update({'W': torch.tensor(W)})

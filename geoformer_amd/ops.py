@@ -189,17 +189,97 @@ class MapBatch:
         return t
 
 
-def pos_encode(x, pe_hwc, out_dtype, out=None):
+class RaggedMapBatch:
+    """A batch of N feature maps of UNEQUAL extents: a list of [C,h_k,w_k] device tensors of one C, dtype, device and layout kind (all
+    channels-last with stride 1 on C, or all contiguous), laid at the top left of a common canvas (default: the per-axis maximum of
+    the extents; entries may repeat).  Read where they lie by gf_pos_encode_ragged / gf_fine_gather_ragged through a device table of
+    gf_map_record (base, strides, extent): canvas positions outside a map's own extent read as zero - the bits of the tensor path on
+    the maps zero-padded at the right and bottom and stacked.  `.shape` is (N, C, H, W) of the CANVAS; otherwise like MapBatch.
+    Raises ValueError on mixed C, dtype, device or layout kind, on an empty list and on a canvas smaller than an extent."""
+
+    def __init__(self, maps, canvas=None):
+        maps = list(maps)
+        if not maps:
+            raise ValueError('RaggedMapBatch: no maps')
+        m0 = maps[0]
+        kinds = set()
+        for m in maps:
+            if m.dim() != 3:
+                raise ValueError(f'RaggedMapBatch: maps are [C,h,w] tensors, got {tuple(m.shape)}')
+            if m.shape[0] != m0.shape[0] or m.dtype != m0.dtype or m.device != m0.device:
+                raise ValueError(f'RaggedMapBatch: the maps of a batch must agree in C, dtype and device: {tuple(m0.shape)} {m0.dtype} {m0.device} '
+                                 f'against {tuple(m.shape)} {m.dtype} {m.device}')
+            kind = {'nhwc'} if m.stride(0) == 1 else set()
+            if m.is_contiguous():
+                kind.add('nchw')                       # a map with C == 1 (or h == w == 1) is both
+            if not kind:
+                raise ValueError(f'RaggedMapBatch: a map must be channels-last (stride 1 on C) or contiguous, got strides {m.stride()}')
+            kinds.add(frozenset(kind))
+        common = frozenset.intersection(*kinds)
+        if not common:
+            raise ValueError('RaggedMapBatch: the maps of a batch must share one layout kind: all channels-last or all contiguous')
+        self.layout = 'nhwc' if 'nhwc' in common else 'nchw'
+        hmax, wmax = max(m.shape[1] for m in maps), max(m.shape[2] for m in maps)
+        H, W = (hmax, wmax) if canvas is None else (int(canvas[0]), int(canvas[1]))
+        if H < hmax or W < wmax:
+            raise ValueError(f'RaggedMapBatch: canvas {H} x {W} is smaller than the largest extents {hmax} x {wmax}')
+        self.maps = maps
+        self.shape = torch.Size((len(maps), m0.shape[0], H, W))
+        self.dtype, self.device = m0.dtype, m0.device
+        self.extents = [(int(m.shape[1]), int(m.shape[2])) for m in maps]
+        self.addresses = [m.data_ptr() for m in maps]
+        low = 256                                           # the largest power of two (bytes, capped) dividing every address
+        for a in self.addresses:
+            low = min(low, a & -a) if a else low
+        self.align = int(low)
+        self._tables = {}
+
+    def __len__(self):
+        return len(self.maps)
+
+    def size(self, dim=None):
+        return self.shape if dim is None else self.shape[dim]
+
+    def records(self):
+        """The N gf_map_record entries as rows of five int64 words: base, sc, sh, sw, h | (w << 32)."""
+        return [[a, *m.stride(), h | (w << 32)] for a, m, (h, w) in zip(self.addresses, self.maps, self.extents)]
+
+    def table(self):
+        """The N records as an int64 [N,5] device tensor, for launches on the CURRENT stream; built like MapBatch.table(): pinned host
+        memory, an asynchronous copy on the current stream, kept per stream by this object."""
+        key = _stream_handle(self.device)
+        t = self._tables.get(key)
+        if t is None:
+            host = torch.tensor(self.records(), dtype=torch.int64).pin_memory()
+            with torch.cuda.device(self.device):
+                t = self._tables[key] = host.to(self.device, non_blocking=True)
+        return t
+
+
+def pos_encode(x, pe_hwc, out_dtype, out=None, mask_out=None):
     """a1.  x [N,C,H,W] (any strides; fp32, fp16 or bf16), pe_hwc fp32 [H,W,C] on the device -> [N, H*W, C] of out_dtype (into `out`
     if given).  Any input / output dtype pair, bf16 -> fp16 and fp16 -> bf16 included: bit-equal to (x.float() + pe).to(out_dtype).
     x may be a MapBatch (N maps in separate allocations, read in place through gf_pos_encode_ptrs): the bits of the tensor path on
-    torch.stack of the maps."""
+    torch.stack of the maps.  x may be a RaggedMapBatch (maps of unequal extents on one canvas, gf_pos_encode_ragged): H, W are the
+    canvas's, the bits are those of the tensor path on the maps zero-padded and stacked, and mask_out (optional, a contiguous uint8 or
+    bool [N,H,W] device tensor) is written by the same launch with the padding mask: true inside each map's own extent."""
     _need_cuda(pe_hwc)
     N, C, H, W = x.shape
     if out is None:
         out = torch.empty(N, H * W, C, dtype=out_dtype, device=x.device)
     elif out.shape != (N, H * W, C) or out.dtype != out_dtype or not out.is_contiguous():
         raise ValueError('out must be a contiguous [N, H*W, C] tensor of out_dtype')
+    if isinstance(x, RaggedMapBatch):
+        _need_cuda(*x.maps, mask_out)
+        if tuple(pe_hwc.shape) != (H, W, C) or pe_hwc.dtype != torch.float32 or not pe_hwc.is_contiguous():
+            raise ValueError(f'pos_encode: the table must be a contiguous fp32 [{H},{W},{C}] tensor (the canvas), got {tuple(pe_hwc.shape)}')
+        if mask_out is not None and (mask_out.shape != (N, H, W) or mask_out.dtype not in (torch.uint8, torch.bool) or not mask_out.is_contiguous()):
+            raise ValueError('mask_out must be a contiguous uint8 or bool [N, H, W] tensor')
+        check(_lib.lib().gf_pos_encode_ragged(_p(x.table()), _dt(x), x.align, _p(pe_hwc), _p(out), _DTYPES[out_dtype], N, C, H, W,
+                                              _p(mask_out), _stream()), 'gf_pos_encode_ragged')
+        return out
+    if mask_out is not None:
+        raise ValueError('pos_encode: mask_out is written for a RaggedMapBatch only (other inputs have no padding)')
     if isinstance(x, MapBatch):
         _need_cuda(*x.maps)
         sc, sh, sw = x.map_stride
@@ -638,10 +718,13 @@ def fine_gather(feat_f0, feat_f1, feat_c0, feat_c1, b_ids, i_ids, j_ids, w0c, w1
     """K7.  feat_f* [N,Cf,H,W] any strides, both of one dtype (fp32, fp16 or bf16; it need not be out_dtype); feat_c* [N,L,CC]
     contiguous of out_dtype; ids int64 [M] (M > 0) -> (win [2M, W*W, Cf], ccat [2M, CC]), both of out_dtype.  The window values
     are feat.float().to(out_dtype) bit for bit (bf16 maps -> fp16 windows: the 'bf16_fp16' mode; no clamp: beyond fp16's range -> inf).
-    feat_f0 / feat_f1 may be MapBatches (both, or neither): the maps are read in place through gf_fine_gather_ptrs, same bits."""
-    tables = isinstance(feat_f0, MapBatch)
-    if tables != isinstance(feat_f1, MapBatch):
-        raise TypeError('fine_gather: feat_f0 and feat_f1 must both be tensors or both be MapBatches')
+    feat_f0 / feat_f1 may be MapBatches (both, or neither): the maps are read in place through gf_fine_gather_ptrs, same bits.
+    Or RaggedMapBatches (both, or neither; gf_fine_gather_ragged): w0c / w1c are the canvases' widths in coarse cells, a tap outside a
+    map's own extent is zero, the bits are those of the tensor path on the maps zero-padded and stacked."""
+    kind0, kind1 = (RaggedMapBatch if isinstance(f, RaggedMapBatch) else MapBatch if isinstance(f, MapBatch) else None for f in (feat_f0, feat_f1))
+    if kind0 is not kind1:
+        raise TypeError('fine_gather: feat_f0 and feat_f1 must both be tensors, both be MapBatches or both be RaggedMapBatches')
+    tables = kind0 is not None
     if tables:
         _need_cuda(*feat_f0.maps, *feat_f1.maps, feat_c0, feat_c1, b_ids)
         if len(feat_f0) != len(feat_f1):
@@ -657,6 +740,12 @@ def fine_gather(feat_f0, feat_f1, feat_c0, feat_c1, b_ids, i_ids, j_ids, w0c, w1
     fc0, fc1 = _contig(feat_c0), _contig(feat_c1)
     if fc0.dtype != out_dtype or fc1.dtype != out_dtype or feat_f0.dtype != feat_f1.dtype:
         raise TypeError('fine_gather: coarse features must already be in out_dtype; fine maps must share a dtype')
+    if kind0 is RaggedMapBatch:
+        check(_lib.lib().gf_fine_gather_ragged(_p(feat_f0.table()), _p(feat_f1.table()), len(feat_f0), _dt(feat_f0), min(feat_f0.align, feat_f1.align),
+                                               Cf, _p(fc0), _p(fc1), _DTYPES[out_dtype], fc0.shape[1], fc1.shape[1], CC, _p(_contig(b_ids)),
+                                               _p(_contig(i_ids)), _p(_contig(j_ids)), M, int(w0c), int(w1c), int(stride), int(window), _p(win),
+                                               _p(ccat), _stream()), 'gf_fine_gather_ragged')
+        return win, ccat
     if tables:
         s0 = (ctypes.c_long * 3)(*feat_f0.map_stride)
         s1 = (ctypes.c_long * 3)(*feat_f1.map_stride)

@@ -37,6 +37,8 @@ typedef enum { GF_F32 = 0, GF_F16 = 1, GF_BF16 = 2 } gf_dtype;
  * version-1 signature (no refinement), new arguments live in gf_ransac_homography_v2, appended at the END. */
 /* 4 (round 4): the fragment stream of gf_conv3x3_nhwc deals the output channels differently (fused.py:pack_conv3x3_stream: a stream packed for
  * version 3 gives wrong channels) and GF_CONV_PAD16 now states that channels 196 .. 223 are padding; new: GF_CONV_S2, gf_lateral_upsample_add_nhwc. */
+/* Still 4 with gf_pos_encode_ptrs / gf_fine_gather_ptrs and gf_pos_encode_ragged / gf_fine_gather_ragged (with gf_map_record): entries appended at
+ * the end change no existing one; a binding that needs them fails at load on the missing symbol (geoformer_amd/_lib.py binds every name). */
 #define GF_ABI_VERSION 4
 int gf_abi_version(void);
 const char* gf_last_error(void);
@@ -601,6 +603,37 @@ int gf_fine_gather_ptrs(const void* const* f0_table, const void* const* f1_table
                         const void* feat_c0, const void* feat_c1, int dtype, int L, int S, int CC, const int64_t* b_ids,
                         const int64_t* i_ids, const int64_t* j_ids, int M, int w0c, int w1c, int stride, int window,
                         void* win_out, void* ccat_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Ragged siblings of the two address-table entries: the N maps of a batch may differ in EXTENT (images of unequal sizes matched in one
+ * padded batch).  The device table holds one record per sample instead of a bare address, and the strides and the extent come from
+ * the record instead of from the arguments.  The maps are anchored at the top left of a common canvas; a canvas position or a window tap
+ * outside a sample's own extent reads as ZERO, whatever lies in memory behind the map - nothing outside [0, h) x [0, w) is ever loaded.
+ * Output bits: those of gf_pos_encode / gf_fine_gather on the maps zero-padded at the right and bottom to the canvas and then stacked.
+ *   gf_pos_encode_ragged   N, C, H, W describe the CANVAS (pe is [H][W][C], out [N][H*W][C]); every record needs h <= H, w <= W (the
+ *            caller's promise, like the addresses).  mask_out: NULL, or uint8 [N][H][W] written by the same launch with
+ *            (y < h_n && x < w_n) - the padding mask the matching path takes.  N <= 65535 (the sample is a grid dimension).
+ *            The form is chosen per sample from its record: 8 channels per lane where sc == 1 and sh, sw are multiples of 8 (and
+ *            x_align >= 32, C % 8 == 0, pe and out 32-byte aligned), one element per lane for other channels-last maps (sc == 1), and
+ *            the 32 x 32 transpose through LDS otherwise (contiguous [C, h, w] maps).
+ *   gf_fine_gather_ragged  one table per side, N records each; H0 / W0 / H1 / W1 and the stride arrays of gf_fine_gather_ptrs are gone
+ *            (w0c / w1c stay: the CANVAS width in coarse cells, which i_ids / j_ids count in).  One wave per window with 16-byte pieces where
+ *            feat_align >= 16, both types are 16-bit and the record has sc == 1 and sh, sw multiples of 8; one workgroup per window otherwise.
+ *   *_align  as in the _ptrs entries: the largest power of two, in bytes, that divides every record's base.
+ *   The tables are read by the launch: they must stay valid (and unchanged) until the launch has run - stream order suffices.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct gf_map_record {
+    const void* base;      /* element [0][0][0] of the map, in DEVICE memory */
+    long sc, sh, sw;       /* element strides of the map viewed as [C, h, w] */
+    int h, w;              /* the map's own extent */
+} gf_map_record;           /* 40 bytes: five 8-byte words, the last one h | (w << 32) */
+
+int gf_pos_encode_ragged(const gf_map_record* x_table, int x_dtype, int x_align, const float* pe, void* out, int out_dtype,
+                         int N, int C, int H, int W, unsigned char* mask_out, void* stream);
+int gf_fine_gather_ragged(const gf_map_record* f0_table, const gf_map_record* f1_table, int N, int feat_dtype, int feat_align, int C,
+                          const void* feat_c0, const void* feat_c1, int dtype, int L, int S, int CC, const int64_t* b_ids,
+                          const int64_t* i_ids, const int64_t* j_ids, int M, int w0c, int w1c, int stride, int window,
+                          void* win_out, void* ccat_out, void* stream);
 
 #ifdef __cplusplus
 }
