@@ -4,7 +4,8 @@
 //                   (b_ids, i_ids / j_ids) (model/loftr_src/loftr/loftr_module/fine_preprocess.py:41-56),
 //                   without materialising the [N, 25*C, L] unfold: each match reads only its own 5x5
 //                   window; plus the gather of the two coarse feature rows that feed down_proj (:61).
-//                   gf_fine_gather_ptrs: the N maps of a side in separate allocations; gf_fine_gather_ragged: of unequal extents too.
+//                   The same kernels behind gf_fine_gather_ptrs (the N maps of a side in separate allocations) and
+//                   gf_fine_gather_ragged (of unequal extents too): the entries differ in the map source they hand over (gf_maps.h).
 //   gf_fine_match   K8 (a14/a15): FineMatching2.forward + get_fine_match (model/fine_matching2.py:21-126):
 //                   25x25 dual-softmax per match, global arg-max, threshold, ordered compaction and the
 //                   fine keypoint arithmetic.
@@ -12,52 +13,41 @@
 
 #include <type_traits>
 
-#include "gf_common.h"
+#include "gf_maps.h"
 
 namespace {
 
+template <typename Src>
 struct FgArgs {
-    const void* f0;          // fine maps viewed as [N, C, H, W] with element strides.  TBL forms (gf_fine_gather_ptrs): f0 / f1 are
-    const void* f1;          // device tables of N per-sample base addresses (const void* const*), s0n / s1n unused
-    long s0n, s0c, s0h, s0w, s1n, s1c, s1h, s1w;
-    int H0, W0, H1, W1, C;   // fine map sizes
+    Src f0, f1;              // the fine maps of the two sides (gf_maps.h), viewed as [C, H, W] per sample
+    int C;
     const void* c0;          // coarse (geo) features [N, L, CC], [N, S, CC]
     const void* c1;
     int L, S, CC;
     const int64_t* b_ids;
     const int64_t* i_ids;
     const int64_t* j_ids;
-    int M, w0c, w1c, stride, W;
+    int M, w0c, w1c, stride, W;   // w0c / w1c: the width in coarse cells (ragged source: of the CANVAS)
     void* win;               // [2M][W*W][C]  (image0 windows first, then image1: torch.cat(..., 0))
     void* ccat;              // [2M][CC]
 };
 
-// Where sample b of one side starts: maps + b * sn (TBL = false), or entry b of a table in device memory (TBL = true) - the one
-// difference between gf_fine_gather and gf_fine_gather_ptrs.  b must be uniform (a scalar register): the entry is then one scalar
-// 8-byte load per workgroup / wave, issued once in front of the window loop.
-template <typename TF, bool TBL>
-__device__ __forceinline__ const TF* fg_sample(const void* maps, int b) {
-    if constexpr (TBL) return (const TF*)((const void* const*)maps)[b];
-    else return (const TF*)maps;      // + b * sn: added where the element offset is formed, as before the table forms existed
-}
-
-// one workgroup per (match, side): thread c < C copies channel c of the 25 window positions
-template <typename TF, typename T, bool TBL>
-__global__ __launch_bounds__(256) void fine_gather(FgArgs a) {
+// one workgroup per (match, side): thread c < C copies channel c of the 25 window positions.  A tap outside the sample's OWN extent is
+// zero like F.unfold's padding - also where memory continues behind the map: nothing outside [0, h) x [0, w) is loaded.
+template <typename TF, typename T, typename Src>
+__global__ __launch_bounds__(256) void fine_gather(FgArgs<Src> a) {
     const int m = blockIdx.x, side = blockIdx.y, t = threadIdx.x;
     const int b = (int)a.b_ids[m];
     const int cell = (int)(side ? a.j_ids[m] : a.i_ids[m]);
     const int wc = side ? a.w1c : a.w0c;
-    const int Hf = side ? a.H1 : a.H0, Wf = side ? a.W1 : a.W0;
-    const TF* f = fg_sample<TF, TBL>(side ? a.f1 : a.f0, b);      // b = b_ids[blockIdx.x]: uniform
-    const long sn = side ? a.s1n : a.s0n, sc = side ? a.s1c : a.s0c, sh = side ? a.s1h : a.s0h, sw = side ? a.s1w : a.s0w;
+    const GfMapView<TF> f = (side ? a.f1 : a.f0).template view<TF>(b);      // b = b_ids[blockIdx.x]: uniform
     const int cy = (cell / wc) * a.stride - a.W / 2, cx = (cell % wc) * a.stride - a.W / 2;
     T* out = (T*)a.win + ((size_t)side * a.M + m) * a.W * a.W * a.C;
     if (t < a.C) {
         for (int k = 0; k < a.W * a.W; ++k) {
             const int y = cy + k / a.W, x = cx + k % a.W;
-            float v = 0.f;                                        // zero padding of F.unfold
-            if (y >= 0 && y < Hf && x >= 0 && x < Wf) v = gf_to_float(f[(TBL ? 0 : b * sn) + t * sc + y * sh + x * sw]);
+            float v = 0.f;                                        // F.unfold's padding, and the canvas beyond the sample's extent
+            if (y >= 0 && y < f.h && x >= 0 && x < f.w) v = gf_to_float(f.base[t * f.sc + y * f.sh + x * f.sw]);
             out[(size_t)k * a.C + t] = gf_from_float<T>(v);
         }
     }
@@ -90,110 +80,40 @@ __device__ __forceinline__ v4u fg_convert8(v4u v) {
 // bf16 value above 65504 becomes +-inf in fp16, one below fp16's subnormal spacing rounds to nearest even (to a subnormal or to
 // a signed zero).  The fp16 mode has the same range through its own backbone.  Same bytes per match as the copy: 16-byte loads
 // and stores either way.  The coarse row is in T already and stays a copy.
-template <typename TF, typename T, bool TBL>
-__global__ __launch_bounds__(256) void fine_gather_rows(FgArgs a) {
+// Whether a map can be read in pieces (channels-last, row and pixel strides multiples of 8 elements) the host has checked - except
+// for the ragged source, where it is known from the sample's record only: a wave whose sample cannot takes the element loop
+// instead - same values, a uniform branch.
+template <typename TF, typename T, typename Src>
+__global__ __launch_bounds__(256) void fine_gather_rows(FgArgs<Src> a) {
     static_assert(sizeof(TF) == 2 && sizeof(T) == 2, "16-byte pieces of 8 elements on both sides");
-    // TBL: the wave's unit is the same in all 64 lanes but the compiler cannot know (it comes from threadIdx): it goes through
-    // v_readfirstlane, so that side, match and sample index are scalars and the table entry is ONE scalar load per wave in front of
-    // the loop - not 64 lanes fetching one address
-    const int lane = threadIdx.x & 63, u0 = blockIdx.x * 4 + (threadIdx.x >> 6), u = TBL ? __builtin_amdgcn_readfirstlane(u0) : u0;
-    if (u >= 2 * a.M) return;
-    const int side = u >= a.M, m = side ? u - a.M : u;
-    const int b = (int)a.b_ids[m];
-    const int cell = (int)(side ? a.j_ids[m] : a.i_ids[m]);
-    const int wc = side ? a.w1c : a.w0c;
-    const int Hf = side ? a.H1 : a.H0, Wf = side ? a.W1 : a.W0;
-    const TF* f = fg_sample<TF, TBL>(side ? a.f1 : a.f0, b);
-    const long sn = side ? a.s1n : a.s0n, sh = side ? a.s1h : a.s0h, sw = side ? a.s1w : a.s0w;
-    const int cy = (cell / wc) * a.stride - a.W / 2, cx = (cell % wc) * a.stride - a.W / 2;
-    const int ppp = a.C / 8, pieces = a.W * a.W * ppp;                  // 16-byte pieces per position / per window
-    T* out = (T*)a.win + (size_t)u * a.W * a.W * a.C;
-    const v4u zero{0u, 0u, 0u, 0u};
-    for (int e = lane; e < pieces; e += 64) {
-        const int k = e / ppp, c8 = (e - k * ppp) * 8, y = cy + k / a.W, x = cx + k % a.W;
-        v4u v = zero;
-        if (y >= 0 && y < Hf && x >= 0 && x < Wf) v = fg_convert8<TF, T>(*reinterpret_cast<const v4u*>(f + (TBL ? 0 : b * sn) + y * sh + x * sw + c8));
-        *reinterpret_cast<v4u*>(out + (size_t)k * a.C + c8) = v;
-    }
-    const T* cf = (const T*)(side ? a.c1 : a.c0) + ((size_t)b * (side ? a.S : a.L) + cell) * a.CC;
-    T* co = (T*)a.ccat + (size_t)u * a.CC;
-    for (int c8 = lane * 8; c8 < a.CC; c8 += 512) *reinterpret_cast<v4u*>(co + c8) = *reinterpret_cast<const v4u*>(cf + c8);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Ragged forms (gf_fine_gather_ragged): the fine maps of a side differ in extent and lie at the top left of a common canvas.  The table
-// entry of sample b is a gf_map_record (base, strides, extent) instead of a bare address, so Hf, Wf and the strides are per sample; a tap
-// outside the sample's OWN extent is zero like F.unfold's padding - also where memory continues behind the map: nothing outside
-// [0, h) x [0, w) is loaded.  b is uniform per workgroup / wave as in the TBL forms: the record is a few scalar loads in front of the loop.
-struct FgRagArgs {
-    const gf_map_record* t0;   // [N] per side, device memory
-    const gf_map_record* t1;
-    int C;
-    const void* c0;            // coarse (geo) features [N, L, CC], [N, S, CC]
-    const void* c1;
-    int L, S, CC;
-    const int64_t* b_ids;
-    const int64_t* i_ids;
-    const int64_t* j_ids;
-    int M, w0c, w1c, stride, W;   // w0c / w1c: the CANVAS width in coarse cells
-    void* win;                 // [2M][W*W][C]
-    void* ccat;                // [2M][CC]
-};
-
-// one workgroup per (match, side): thread c < C copies channel c of the window positions
-template <typename TF, typename T>
-__global__ __launch_bounds__(256) void fine_gather_ragged(FgRagArgs a) {
-    const int m = blockIdx.x, side = blockIdx.y, t = threadIdx.x;
-    const int b = (int)a.b_ids[m];
-    const int cell = (int)(side ? a.j_ids[m] : a.i_ids[m]);
-    const int wc = side ? a.w1c : a.w0c;
-    const gf_map_record r = (side ? a.t1 : a.t0)[b];              // b = b_ids[blockIdx.x]: uniform
-    const TF* f = (const TF*)r.base;
-    const int cy = (cell / wc) * a.stride - a.W / 2, cx = (cell % wc) * a.stride - a.W / 2;
-    T* out = (T*)a.win + ((size_t)side * a.M + m) * a.W * a.W * a.C;
-    if (t < a.C) {
-        for (int k = 0; k < a.W * a.W; ++k) {
-            const int y = cy + k / a.W, x = cx + k % a.W;
-            float v = 0.f;                                        // F.unfold's padding, and the canvas beyond the sample's extent
-            if (y >= 0 && y < r.h && x >= 0 && x < r.w) v = gf_to_float(f[t * r.sc + y * r.sh + x * r.sw]);
-            out[(size_t)k * a.C + t] = gf_from_float<T>(v);
-        }
-    }
-    const T* cf = (const T*)(side ? a.c1 : a.c0) + ((size_t)b * (side ? a.S : a.L) + cell) * a.CC;
-    T* co = (T*)a.ccat + ((size_t)side * a.M + m) * a.CC;
-    for (int c = t; c < a.CC; c += blockDim.x) co[c] = cf[c];
-}
-
-// the 16-bit form: one wave per (match, side), 16-byte pieces (fine_gather_rows above).  Whether a sample's map can be read in pieces
-// (channels-last, row and pixel strides multiples of 8 elements) is known from its record only: a wave whose sample cannot takes the
-// element loop instead - same values, a uniform branch.
-template <typename TF, typename T>
-__global__ __launch_bounds__(256) void fine_gather_rows_ragged(FgRagArgs a) {
-    static_assert(sizeof(TF) == 2 && sizeof(T) == 2, "16-byte pieces of 8 elements on both sides");
+    // the wave's unit is the same in all 64 lanes but the compiler cannot know (it comes from threadIdx): it goes through
+    // v_readfirstlane, so that side, match and sample index are scalars and the sample's view is a few scalar loads per wave in front
+    // of the loop - not 64 lanes fetching one address
     const int lane = threadIdx.x & 63, u = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
     if (u >= 2 * a.M) return;
     const int side = u >= a.M, m = side ? u - a.M : u;
     const int b = (int)a.b_ids[m];
     const int cell = (int)(side ? a.j_ids[m] : a.i_ids[m]);
     const int wc = side ? a.w1c : a.w0c;
-    const gf_map_record r = (side ? a.t1 : a.t0)[b];
-    const TF* f = (const TF*)r.base;
+    const GfMapView<TF> f = (side ? a.f1 : a.f0).template view<TF>(b);
     const int cy = (cell / wc) * a.stride - a.W / 2, cx = (cell % wc) * a.stride - a.W / 2;
     T* out = (T*)a.win + (size_t)u * a.W * a.W * a.C;
-    if (r.sc == 1 && r.sh % 8 == 0 && r.sw % 8 == 0) {
+    bool in_pieces = true;
+    if constexpr (Src::per_sample) in_pieces = f.sc == 1 && f.sh % 8 == 0 && f.sw % 8 == 0;
+    if (in_pieces) {
         const int ppp = a.C / 8, pieces = a.W * a.W * ppp;              // 16-byte pieces per position / per window
         const v4u zero{0u, 0u, 0u, 0u};
         for (int e = lane; e < pieces; e += 64) {
             const int k = e / ppp, c8 = (e - k * ppp) * 8, y = cy + k / a.W, x = cx + k % a.W;
             v4u v = zero;
-            if (y >= 0 && y < r.h && x >= 0 && x < r.w) v = fg_convert8<TF, T>(*reinterpret_cast<const v4u*>(f + y * r.sh + x * r.sw + c8));
+            if (y >= 0 && y < f.h && x >= 0 && x < f.w) v = fg_convert8<TF, T>(*reinterpret_cast<const v4u*>(f.base + y * f.sh + x * f.sw + c8));
             *reinterpret_cast<v4u*>(out + (size_t)k * a.C + c8) = v;
         }
-    } else {
+    } else if constexpr (Src::per_sample) {
         for (int e = lane; e < a.W * a.W * a.C; e += 64) {
             const int k = e / a.C, c = e - k * a.C, y = cy + k / a.W, x = cx + k % a.W;
             float v = 0.f;
-            if (y >= 0 && y < r.h && x >= 0 && x < r.w) v = gf_to_float(f[c * r.sc + y * r.sh + x * r.sw]);
+            if (y >= 0 && y < f.h && x >= 0 && x < f.w) v = gf_to_float(f.base[c * f.sc + y * f.sh + x * f.sw]);
             out[e] = gf_from_float<T>(v);
         }
     }
@@ -427,76 +347,63 @@ __global__ __launch_bounds__(1024) void fine_compact(FmArgs a) {
     a.m_bids[pos] = b;
 }
 
-// feat_align (TBL): the largest power of two, in bytes, that divides EVERY entry of both tables - the caller built them and knows
-template <typename TF, typename T, bool TBL>
-int fg_launch(const FgArgs& a, hipStream_t st, unsigned feat_align) {
+// feat_align (table sources): the largest power of two, in bytes, that divides EVERY entry of both tables - the caller built them and knows
+template <typename TF, typename T, typename Src>
+int fg_launch(const FgArgs<Src>& a, hipStream_t st, unsigned feat_align) {
     if constexpr (sizeof(TF) == 2 && sizeof(T) == 2) {
-        const bool maps16 = TBL ? feat_align % 16 == 0
-                                : (uintptr_t)a.f0 % 16 == 0 && (uintptr_t)a.f1 % 16 == 0 && a.s0n % 8 == 0 && a.s1n % 8 == 0;
-        const bool rows16 = a.s0c == 1 && a.s1c == 1 && a.C % 8 == 0 && a.CC % 8 == 0 && maps16 &&
-                            (uintptr_t)a.c0 % 16 == 0 && (uintptr_t)a.c1 % 16 == 0 && (uintptr_t)a.win % 16 == 0 && (uintptr_t)a.ccat % 16 == 0 &&
-                            a.s0h % 8 == 0 && a.s0w % 8 == 0 && a.s1h % 8 == 0 && a.s1w % 8 == 0;
+        bool rows16 = a.C % 8 == 0 && a.CC % 8 == 0 && a.f0.bases_aligned(16, 2, feat_align) && a.f1.bases_aligned(16, 2, feat_align) &&
+                      (uintptr_t)a.c0 % 16 == 0 && (uintptr_t)a.c1 % 16 == 0 && (uintptr_t)a.win % 16 == 0 && (uintptr_t)a.ccat % 16 == 0;
+        if constexpr (!Src::per_sample)          // per-sample strides: each wave looks at its own record
+            rows16 = rows16 && a.f0.sc == 1 && a.f1.sc == 1 && a.f0.sh % 8 == 0 && a.f0.sw % 8 == 0 && a.f1.sh % 8 == 0 && a.f1.sw % 8 == 0;
         if (rows16) {
-            fine_gather_rows<TF, T, TBL><<<(2 * a.M + 3) / 4, 256, 0, st>>>(a);
+            fine_gather_rows<TF, T, Src><<<(2 * a.M + 3) / 4, 256, 0, st>>>(a);
             GF_CHECK_LAUNCH();
             return GF_OK;
         }
     }
-    fine_gather<TF, T, TBL><<<dim3(a.M, 2), 256, 0, st>>>(a);
+    fine_gather<TF, T, Src><<<dim3(a.M, 2), 256, 0, st>>>(a);
     GF_CHECK_LAUNCH();
     return GF_OK;
 }
 
-template <typename TF, bool TBL>
-int fg_launch_to(int dtype, const FgArgs& a, hipStream_t st, unsigned feat_align) {
-    return dtype == GF_F32 ? fg_launch<TF, float, TBL>(a, st, feat_align)
-                           : dtype == GF_F16 ? fg_launch<TF, _Float16, TBL>(a, st, feat_align) : fg_launch<TF, gf_bf16, TBL>(a, st, feat_align);
+template <typename TF, typename Src>
+int fg_launch_to(int dtype, const FgArgs<Src>& a, hipStream_t st, unsigned feat_align) {
+    return dtype == GF_F32 ? fg_launch<TF, float>(a, st, feat_align)
+                           : dtype == GF_F16 ? fg_launch<TF, _Float16>(a, st, feat_align) : fg_launch<TF, gf_bf16>(a, st, feat_align);
 }
 
-template <bool TBL>
-int fg_dispatch(int feat_dtype, int dtype, const FgArgs& a, hipStream_t st, unsigned feat_align) {
-    if (feat_dtype == GF_F32) return fg_launch_to<float, TBL>(dtype, a, st, feat_align);
-    if (feat_dtype == GF_F16) return fg_launch_to<_Float16, TBL>(dtype, a, st, feat_align);
-    return fg_launch_to<gf_bf16, TBL>(dtype, a, st, feat_align);
-}
-
-template <typename TF, typename T>
-int fg_ragged_launch(const FgRagArgs& a, hipStream_t st, unsigned feat_align) {
-    if constexpr (sizeof(TF) == 2 && sizeof(T) == 2) {
-        const bool rows16 = feat_align % 16 == 0 && a.C % 8 == 0 && a.CC % 8 == 0 && (uintptr_t)a.c0 % 16 == 0 && (uintptr_t)a.c1 % 16 == 0 &&
-                            (uintptr_t)a.win % 16 == 0 && (uintptr_t)a.ccat % 16 == 0;
-        if (rows16) {
-            fine_gather_rows_ragged<TF, T><<<(2 * a.M + 3) / 4, 256, 0, st>>>(a);
-            GF_CHECK_LAUNCH();
-            return GF_OK;
-        }
-    }
-    fine_gather_ragged<TF, T><<<dim3(a.M, 2), 256, 0, st>>>(a);
-    GF_CHECK_LAUNCH();
-    return GF_OK;
-}
-
-template <typename TF>
-int fg_ragged_to(int dtype, const FgRagArgs& a, hipStream_t st, unsigned feat_align) {
-    return dtype == GF_F32 ? fg_ragged_launch<TF, float>(a, st, feat_align)
-                           : dtype == GF_F16 ? fg_ragged_launch<TF, _Float16>(a, st, feat_align) : fg_ragged_launch<TF, gf_bf16>(a, st, feat_align);
+template <typename Src>
+int fg_dispatch(int feat_dtype, int dtype, const FgArgs<Src>& a, void* stream, int feat_align) {
+    hipStream_t st = (hipStream_t)stream;
+    if (feat_dtype == GF_F32) return fg_launch_to<float>(dtype, a, st, (unsigned)feat_align);
+    if (feat_dtype == GF_F16) return fg_launch_to<_Float16>(dtype, a, st, (unsigned)feat_align);
+    return fg_launch_to<gf_bf16>(dtype, a, st, (unsigned)feat_align);
 }
 
 }   // namespace
+
+// The checks of the three gf_fine_gather entries, in one order; a macro, so that GF_CHECK_ARG's message names the entry that was called.
+// maps_ok: the entry's own map arguments are non-null;  n_ok / n_max_ok / feat_align: the table entries' (true / true / 1 otherwise).
+#define FG_CHECK_ARGS(maps_ok, n_ok, n_max_ok, feat_align)                                                                                 \
+    GF_CHECK_ARG((maps_ok) && feat_c0 && feat_c1 && b_ids && i_ids && j_ids && win_out && ccat_out, "null pointer");                       \
+    GF_CHECK_ARG(n_ok, "empty table");                                                                                                     \
+    GF_CHECK_ARG(n_max_ok, "at most 65535 table entries");                                                                                 \
+    GF_CHECK_ARG(M > 0, "M must be > 0 (the M == 0 early return of fine_preprocess.py:35-38 is the caller's)");                            \
+    GF_CHECK_ARG(C > 0 && C <= 256 && window > 0 && stride > 0 && w0c > 0 && w1c > 0, "bad sizes");                                        \
+    GF_CHECK_ARG((feat_align) > 0 && ((feat_align) & ((feat_align) - 1)) == 0, "feat_align must be a power of two");                       \
+    GF_CHECK_ARG(feat_dtype >= GF_F32 && feat_dtype <= GF_BF16 && dtype >= GF_F32 && dtype <= GF_BF16, "bad dtype")
+// the arguments behind the two map sources, under the names all three entries give them
+#define FG_COMMON_ARGS C, feat_c0, feat_c1, L, S, CC, b_ids, i_ids, j_ids, M, w0c, w1c, stride, window, win_out, ccat_out
 
 extern "C" int gf_fine_gather(const void* feat_f0, const void* feat_f1, int feat_dtype, const long* strides0,
                               const long* strides1, int H0, int W0, int H1, int W1, int C, const void* feat_c0,
                               const void* feat_c1, int dtype, int L, int S, int CC, const int64_t* b_ids,
                               const int64_t* i_ids, const int64_t* j_ids, int M, int w0c, int w1c, int stride,
                               int window, void* win_out, void* ccat_out, void* stream) {
-    GF_CHECK_ARG(feat_f0 && feat_f1 && strides0 && strides1 && feat_c0 && feat_c1 && b_ids && i_ids && j_ids && win_out && ccat_out, "null pointer");
-    GF_CHECK_ARG(M > 0, "M must be > 0 (the M == 0 early return of fine_preprocess.py:35-38 is the caller's)");
-    GF_CHECK_ARG(C > 0 && C <= 256 && window > 0 && stride > 0 && w0c > 0 && w1c > 0, "bad sizes");
-    GF_CHECK_ARG(feat_dtype >= GF_F32 && feat_dtype <= GF_BF16 && dtype >= GF_F32 && dtype <= GF_BF16, "bad dtype");
-    FgArgs a{feat_f0, feat_f1, strides0[0], strides0[1], strides0[2], strides0[3], strides1[0], strides1[1], strides1[2],
-             strides1[3], H0, W0, H1, W1, C, feat_c0, feat_c1, L, S, CC, b_ids, i_ids, j_ids, M, w0c, w1c, stride, window,
-             win_out, ccat_out};
-    return fg_dispatch<false>(feat_dtype, dtype, a, (hipStream_t)stream, 0);
+    FG_CHECK_ARGS(feat_f0 && feat_f1 && strides0 && strides1, true, true, 1);
+    FgArgs<GfTensorMaps> a{{feat_f0, strides0[0], strides0[1], strides0[2], strides0[3], H0, W0},
+                           {feat_f1, strides1[0], strides1[1], strides1[2], strides1[3], H1, W1}, FG_COMMON_ARGS};
+    return fg_dispatch(feat_dtype, dtype, a, stream, 0);
 }
 
 extern "C" int gf_fine_gather_ptrs(const void* const* f0_table, const void* const* f1_table, int N, int feat_dtype, int feat_align,
@@ -504,34 +411,19 @@ extern "C" int gf_fine_gather_ptrs(const void* const* f0_table, const void* cons
                                    const void* feat_c0, const void* feat_c1, int dtype, int L, int S, int CC, const int64_t* b_ids,
                                    const int64_t* i_ids, const int64_t* j_ids, int M, int w0c, int w1c, int stride, int window,
                                    void* win_out, void* ccat_out, void* stream) {
-    GF_CHECK_ARG(f0_table && f1_table && strides0 && strides1 && feat_c0 && feat_c1 && b_ids && i_ids && j_ids && win_out && ccat_out, "null pointer");
-    GF_CHECK_ARG(N > 0, "empty table");
-    GF_CHECK_ARG(M > 0, "M must be > 0 (the M == 0 early return of fine_preprocess.py:35-38 is the caller's)");
-    GF_CHECK_ARG(C > 0 && C <= 256 && window > 0 && stride > 0 && w0c > 0 && w1c > 0, "bad sizes");
-    GF_CHECK_ARG(feat_align > 0 && (feat_align & (feat_align - 1)) == 0, "feat_align must be a power of two");
-    GF_CHECK_ARG(feat_dtype >= GF_F32 && feat_dtype <= GF_BF16 && dtype >= GF_F32 && dtype <= GF_BF16, "bad dtype");
-    FgArgs a{f0_table, f1_table, 0, strides0[0], strides0[1], strides0[2], 0, strides1[0], strides1[1], strides1[2],
-             H0, W0, H1, W1, C, feat_c0, feat_c1, L, S, CC, b_ids, i_ids, j_ids, M, w0c, w1c, stride, window,
-             win_out, ccat_out};
-    return fg_dispatch<true>(feat_dtype, dtype, a, (hipStream_t)stream, (unsigned)feat_align);
+    FG_CHECK_ARGS(f0_table && f1_table && strides0 && strides1, N > 0, true, feat_align);
+    FgArgs<GfTableMaps> a{{f0_table, strides0[0], strides0[1], strides0[2], H0, W0},
+                          {f1_table, strides1[0], strides1[1], strides1[2], H1, W1}, FG_COMMON_ARGS};
+    return fg_dispatch(feat_dtype, dtype, a, stream, feat_align);
 }
 
 extern "C" int gf_fine_gather_ragged(const gf_map_record* f0_table, const gf_map_record* f1_table, int N, int feat_dtype, int feat_align, int C,
                                      const void* feat_c0, const void* feat_c1, int dtype, int L, int S, int CC, const int64_t* b_ids,
                                      const int64_t* i_ids, const int64_t* j_ids, int M, int w0c, int w1c, int stride, int window,
                                      void* win_out, void* ccat_out, void* stream) {
-    GF_CHECK_ARG(f0_table && f1_table && feat_c0 && feat_c1 && b_ids && i_ids && j_ids && win_out && ccat_out, "null pointer");
-    GF_CHECK_ARG(N > 0, "empty table");
-    GF_CHECK_ARG(N <= 65535, "at most 65535 table entries");
-    GF_CHECK_ARG(M > 0, "M must be > 0 (the M == 0 early return of fine_preprocess.py:35-38 is the caller's)");
-    GF_CHECK_ARG(C > 0 && C <= 256 && window > 0 && stride > 0 && w0c > 0 && w1c > 0, "bad sizes");
-    GF_CHECK_ARG(feat_align > 0 && (feat_align & (feat_align - 1)) == 0, "feat_align must be a power of two");
-    GF_CHECK_ARG(feat_dtype >= GF_F32 && feat_dtype <= GF_BF16 && dtype >= GF_F32 && dtype <= GF_BF16, "bad dtype");
-    FgRagArgs a{f0_table, f1_table, C, feat_c0, feat_c1, L, S, CC, b_ids, i_ids, j_ids, M, w0c, w1c, stride, window, win_out, ccat_out};
-    hipStream_t st = (hipStream_t)stream;
-    if (feat_dtype == GF_F32) return fg_ragged_to<float>(dtype, a, st, (unsigned)feat_align);
-    if (feat_dtype == GF_F16) return fg_ragged_to<_Float16>(dtype, a, st, (unsigned)feat_align);
-    return fg_ragged_to<gf_bf16>(dtype, a, st, (unsigned)feat_align);
+    FG_CHECK_ARGS(f0_table && f1_table, N > 0, N <= 65535, feat_align);
+    FgArgs<GfRaggedMaps> a{{f0_table}, {f1_table}, FG_COMMON_ARGS};
+    return fg_dispatch(feat_dtype, dtype, a, stream, feat_align);
 }
 
 extern "C" size_t gf_fine_match_workspace_bytes(int M) {

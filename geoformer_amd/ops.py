@@ -135,32 +135,14 @@ def dual_softmax_match(f0, f1, temperature, thr, hw0_c, hw1_c, scale, mask0=None
             'mkpts0_c': mk[0], 'mkpts1_c': mk[1], 'counts': counts}
 
 
-def _i32p(t):
-    return _p(t)
+class _MapTable:
+    """What MapBatch and RaggedMapBatch share: the list of maps, the tensor-like `.shape` / `.dtype` / `.device`, the maps' addresses with
+    their common alignment, and the device table the kernels read - one row of int64 words per map, which the subclass's _rows() gives."""
 
-
-class MapBatch:
-    """A batch of N feature maps that lie in SEPARATE allocations: a list of [C,H,W] device tensors of one shape, dtype, device and
-    stride triple (entries may repeat: one query map against N candidates), read where they lie by the address-table entries
-    gf_pos_encode_ptrs / gf_fine_gather_ptrs - `pos_encode` and `fine_gather` below take it in place of the [N,C,H,W] tensor.
-    Behaves like that tensor for `.shape`, `.dtype` and `.device`, and nothing more: the two ops are the only readers.
-    Raises ValueError when the maps differ in shape, dtype, device or strides."""
-
-    def __init__(self, maps):
-        maps = list(maps)
-        if not maps:
-            raise ValueError('MapBatch: no maps')
-        m0 = maps[0]
-        if m0.dim() != 3:
-            raise ValueError(f'MapBatch: maps are [C,H,W] tensors, got {tuple(m0.shape)}')
-        for m in maps[1:]:
-            if m.shape != m0.shape or m.dtype != m0.dtype or m.device != m0.device or m.stride() != m0.stride():
-                raise ValueError(f'MapBatch: the maps of a batch must agree in shape, dtype, device and strides: {tuple(m0.shape)} {m0.dtype} '
-                                 f'{m0.device} strides {m0.stride()} against {tuple(m.shape)} {m.dtype} {m.device} strides {m.stride()}')
+    def __init__(self, maps, shape):
         self.maps = maps
-        self.shape = torch.Size((len(maps),) + tuple(m0.shape))
-        self.dtype, self.device = m0.dtype, m0.device
-        self.map_stride = tuple(m0.stride())                # (sc, sh, sw), elements
+        self.shape = torch.Size(shape)
+        self.dtype, self.device = maps[0].dtype, maps[0].device
         self.addresses = [m.data_ptr() for m in maps]
         low = 256                                           # the largest power of two (bytes, capped) dividing every address
         for a in self.addresses:
@@ -175,7 +157,7 @@ class MapBatch:
         return self.shape if dim is None else self.shape[dim]
 
     def table(self):
-        """The N addresses as an int64 device tensor, for launches on the CURRENT stream.  No device synchronisation: the addresses are
+        """The N rows as an int64 device tensor, for launches on the CURRENT stream.  No device synchronisation: the rows are
         written into a pinned host tensor and copied asynchronously on the current stream (torch's pinned-memory allocator holds the
         host block back until that copy has run).  Kept per stream by this object, so it lives as long as the batch does and at least
         until the launches that read it have been enqueued; freed afterwards, the caching allocator's stream order keeps the block from
@@ -183,18 +165,45 @@ class MapBatch:
         key = _stream_handle(self.device)
         t = self._tables.get(key)
         if t is None:
-            host = torch.tensor(self.addresses, dtype=torch.int64).pin_memory()
+            host = torch.tensor(self._rows(), dtype=torch.int64).pin_memory()
             with torch.cuda.device(self.device):
                 t = self._tables[key] = host.to(self.device, non_blocking=True)
         return t
 
 
-class RaggedMapBatch:
+class MapBatch(_MapTable):
+    """A batch of N feature maps that lie in SEPARATE allocations: a list of [C,H,W] device tensors of one shape, dtype, device and
+    stride triple (entries may repeat: one query map against N candidates), read where they lie by the address-table entries
+    gf_pos_encode_ptrs / gf_fine_gather_ptrs - `pos_encode` and `fine_gather` below take it in place of the [N,C,H,W] tensor.
+    Behaves like that tensor for `.shape`, `.dtype` and `.device`, and nothing more: the two ops are the only readers.
+    `table()`: the N addresses as an int64 [N] device tensor.
+    Raises ValueError when the maps differ in shape, dtype, device or strides."""
+
+    def __init__(self, maps):
+        maps = list(maps)
+        if not maps:
+            raise ValueError('MapBatch: no maps')
+        m0 = maps[0]
+        if m0.dim() != 3:
+            raise ValueError(f'MapBatch: maps are [C,H,W] tensors, got {tuple(m0.shape)}')
+        for m in maps[1:]:
+            if m.shape != m0.shape or m.dtype != m0.dtype or m.device != m0.device or m.stride() != m0.stride():
+                raise ValueError(f'MapBatch: the maps of a batch must agree in shape, dtype, device and strides: {tuple(m0.shape)} {m0.dtype} '
+                                 f'{m0.device} strides {m0.stride()} against {tuple(m.shape)} {m.dtype} {m.device} strides {m.stride()}')
+        super().__init__(maps, (len(maps),) + tuple(m0.shape))
+        self.map_stride = tuple(m0.stride())                # (sc, sh, sw), elements
+
+    def _rows(self):
+        return self.addresses
+
+
+class RaggedMapBatch(_MapTable):
     """A batch of N feature maps of UNEQUAL extents: a list of [C,h_k,w_k] device tensors of one C, dtype, device and layout kind (all
     channels-last with stride 1 on C, or all contiguous), laid at the top left of a common canvas (default: the per-axis maximum of
     the extents; entries may repeat).  Read where they lie by gf_pos_encode_ragged / gf_fine_gather_ragged through a device table of
     gf_map_record (base, strides, extent): canvas positions outside a map's own extent read as zero - the bits of the tensor path on
     the maps zero-padded at the right and bottom and stacked.  `.shape` is (N, C, H, W) of the CANVAS; otherwise like MapBatch.
+    `table()`: the N records as an int64 [N,5] device tensor.
     Raises ValueError on mixed C, dtype, device or layout kind, on an empty list and on a canvas smaller than an extent."""
 
     def __init__(self, maps, canvas=None):
@@ -218,42 +227,19 @@ class RaggedMapBatch:
         common = frozenset.intersection(*kinds)
         if not common:
             raise ValueError('RaggedMapBatch: the maps of a batch must share one layout kind: all channels-last or all contiguous')
-        self.layout = 'nhwc' if 'nhwc' in common else 'nchw'
         hmax, wmax = max(m.shape[1] for m in maps), max(m.shape[2] for m in maps)
         H, W = (hmax, wmax) if canvas is None else (int(canvas[0]), int(canvas[1]))
         if H < hmax or W < wmax:
             raise ValueError(f'RaggedMapBatch: canvas {H} x {W} is smaller than the largest extents {hmax} x {wmax}')
-        self.maps = maps
-        self.shape = torch.Size((len(maps), m0.shape[0], H, W))
-        self.dtype, self.device = m0.dtype, m0.device
+        super().__init__(maps, (len(maps), m0.shape[0], H, W))
+        self.layout = 'nhwc' if 'nhwc' in common else 'nchw'
         self.extents = [(int(m.shape[1]), int(m.shape[2])) for m in maps]
-        self.addresses = [m.data_ptr() for m in maps]
-        low = 256                                           # the largest power of two (bytes, capped) dividing every address
-        for a in self.addresses:
-            low = min(low, a & -a) if a else low
-        self.align = int(low)
-        self._tables = {}
-
-    def __len__(self):
-        return len(self.maps)
-
-    def size(self, dim=None):
-        return self.shape if dim is None else self.shape[dim]
 
     def records(self):
         """The N gf_map_record entries as rows of five int64 words: base, sc, sh, sw, h | (w << 32)."""
         return [[a, *m.stride(), h | (w << 32)] for a, m, (h, w) in zip(self.addresses, self.maps, self.extents)]
 
-    def table(self):
-        """The N records as an int64 [N,5] device tensor, for launches on the CURRENT stream; built like MapBatch.table(): pinned host
-        memory, an asynchronous copy on the current stream, kept per stream by this object."""
-        key = _stream_handle(self.device)
-        t = self._tables.get(key)
-        if t is None:
-            host = torch.tensor(self.records(), dtype=torch.int64).pin_memory()
-            with torch.cuda.device(self.device):
-                t = self._tables[key] = host.to(self.device, non_blocking=True)
-        return t
+    _rows = records
 
 
 def pos_encode(x, pe_hwc, out_dtype, out=None, mask_out=None):
@@ -264,32 +250,26 @@ def pos_encode(x, pe_hwc, out_dtype, out=None, mask_out=None):
     canvas's, the bits are those of the tensor path on the maps zero-padded and stacked, and mask_out (optional, a contiguous uint8 or
     bool [N,H,W] device tensor) is written by the same launch with the padding mask: true inside each map's own extent."""
     _need_cuda(pe_hwc)
+    ragged, table = isinstance(x, RaggedMapBatch), isinstance(x, MapBatch)
     N, C, H, W = x.shape
     if out is None:
         out = torch.empty(N, H * W, C, dtype=out_dtype, device=x.device)
     elif out.shape != (N, H * W, C) or out.dtype != out_dtype or not out.is_contiguous():
         raise ValueError('out must be a contiguous [N, H*W, C] tensor of out_dtype')
-    if isinstance(x, RaggedMapBatch):
-        _need_cuda(*x.maps, mask_out)
-        if tuple(pe_hwc.shape) != (H, W, C) or pe_hwc.dtype != torch.float32 or not pe_hwc.is_contiguous():
-            raise ValueError(f'pos_encode: the table must be a contiguous fp32 [{H},{W},{C}] tensor (the canvas), got {tuple(pe_hwc.shape)}')
-        if mask_out is not None and (mask_out.shape != (N, H, W) or mask_out.dtype not in (torch.uint8, torch.bool) or not mask_out.is_contiguous()):
-            raise ValueError('mask_out must be a contiguous uint8 or bool [N, H, W] tensor')
-        check(_lib.lib().gf_pos_encode_ragged(_p(x.table()), _dt(x), x.align, _p(pe_hwc), _p(out), _DTYPES[out_dtype], N, C, H, W,
-                                              _p(mask_out), _stream()), 'gf_pos_encode_ragged')
-        return out
-    if mask_out is not None:
+    if mask_out is not None and not ragged:
         raise ValueError('pos_encode: mask_out is written for a RaggedMapBatch only (other inputs have no padding)')
-    if isinstance(x, MapBatch):
-        _need_cuda(*x.maps)
-        sc, sh, sw = x.map_stride
-        check(_lib.lib().gf_pos_encode_ptrs(_p(x.table()), _dt(x), sc, sh, sw, x.align, _p(pe_hwc), _p(out), _DTYPES[out_dtype], N, C, H, W,
-                                            _stream()), 'gf_pos_encode_ptrs')
-        return out
-    _need_cuda(x)
-    sn, sc, sh, sw = x.stride()
-    check(_lib.lib().gf_pos_encode(_p(x), _dt(x), sn, sc, sh, sw, _p(pe_hwc), _p(out), _DTYPES[out_dtype], N, C, H, W,
-                                   _stream()), 'gf_pos_encode')
+    _need_cuda(*(x.maps if ragged or table else (x,)), mask_out)
+    if ragged and (tuple(pe_hwc.shape) != (H, W, C) or pe_hwc.dtype != torch.float32 or not pe_hwc.is_contiguous()):
+        raise ValueError(f'pos_encode: the table must be a contiguous fp32 [{H},{W},{C}] tensor (the canvas), got {tuple(pe_hwc.shape)}')
+    if mask_out is not None and (mask_out.shape != (N, H, W) or mask_out.dtype not in (torch.uint8, torch.bool) or not mask_out.is_contiguous()):
+        raise ValueError('mask_out must be a contiguous uint8 or bool [N, H, W] tensor')
+    L_, rest = _lib.lib(), (_p(pe_hwc), _p(out), _DTYPES[out_dtype], N, C, H, W)
+    if ragged:
+        check(L_.gf_pos_encode_ragged(_p(x.table()), _dt(x), x.align, *rest, _p(mask_out), _stream()), 'gf_pos_encode_ragged')
+    elif table:
+        check(L_.gf_pos_encode_ptrs(_p(x.table()), _dt(x), *x.map_stride, x.align, *rest, _stream()), 'gf_pos_encode_ptrs')
+    else:
+        check(L_.gf_pos_encode(_p(x), _dt(x), *x.stride(), *rest, _stream()), 'gf_pos_encode')
     return out
 
 
@@ -724,8 +704,7 @@ def fine_gather(feat_f0, feat_f1, feat_c0, feat_c1, b_ids, i_ids, j_ids, w0c, w1
     kind0, kind1 = (RaggedMapBatch if isinstance(f, RaggedMapBatch) else MapBatch if isinstance(f, MapBatch) else None for f in (feat_f0, feat_f1))
     if kind0 is not kind1:
         raise TypeError('fine_gather: feat_f0 and feat_f1 must both be tensors, both be MapBatches or both be RaggedMapBatches')
-    tables = kind0 is not None
-    if tables:
+    if kind0 is not None:
         _need_cuda(*feat_f0.maps, *feat_f1.maps, feat_c0, feat_c1, b_ids)
         if len(feat_f0) != len(feat_f1):
             raise ValueError(f'fine_gather: {len(feat_f0)} maps on side 0, {len(feat_f1)} on side 1')
@@ -740,28 +719,23 @@ def fine_gather(feat_f0, feat_f1, feat_c0, feat_c1, b_ids, i_ids, j_ids, w0c, w1
     fc0, fc1 = _contig(feat_c0), _contig(feat_c1)
     if fc0.dtype != out_dtype or fc1.dtype != out_dtype or feat_f0.dtype != feat_f1.dtype:
         raise TypeError('fine_gather: coarse features must already be in out_dtype; fine maps must share a dtype')
+    ids = [_contig(t) for t in (b_ids, i_ids, j_ids)]
+    L_ = _lib.lib()
+    rest = (Cf, _p(fc0), _p(fc1), _DTYPES[out_dtype], fc0.shape[1], fc1.shape[1], CC, *map(_p, ids), M, int(w0c), int(w1c), int(stride),
+            int(window), _p(win), _p(ccat), _stream())
     if kind0 is RaggedMapBatch:
-        check(_lib.lib().gf_fine_gather_ragged(_p(feat_f0.table()), _p(feat_f1.table()), len(feat_f0), _dt(feat_f0), min(feat_f0.align, feat_f1.align),
-                                               Cf, _p(fc0), _p(fc1), _DTYPES[out_dtype], fc0.shape[1], fc1.shape[1], CC, _p(_contig(b_ids)),
-                                               _p(_contig(i_ids)), _p(_contig(j_ids)), M, int(w0c), int(w1c), int(stride), int(window), _p(win),
-                                               _p(ccat), _stream()), 'gf_fine_gather_ragged')
+        check(L_.gf_fine_gather_ragged(_p(feat_f0.table()), _p(feat_f1.table()), len(feat_f0), _dt(feat_f0), min(feat_f0.align, feat_f1.align),
+                                       *rest), 'gf_fine_gather_ragged')
         return win, ccat
-    if tables:
-        s0 = (ctypes.c_long * 3)(*feat_f0.map_stride)
-        s1 = (ctypes.c_long * 3)(*feat_f1.map_stride)
-        check(_lib.lib().gf_fine_gather_ptrs(_p(feat_f0.table()), _p(feat_f1.table()), len(feat_f0), _dt(feat_f0), min(feat_f0.align, feat_f1.align),
-                                             ctypes.cast(s0, ctypes.c_void_p), ctypes.cast(s1, ctypes.c_void_p), feat_f0.shape[2],
-                                             feat_f0.shape[3], feat_f1.shape[2], feat_f1.shape[3], Cf, _p(fc0), _p(fc1), _DTYPES[out_dtype],
-                                             fc0.shape[1], fc1.shape[1], CC, _p(_contig(b_ids)), _p(_contig(i_ids)), _p(_contig(j_ids)), M,
-                                             int(w0c), int(w1c), int(stride), int(window), _p(win), _p(ccat), _stream()), 'gf_fine_gather_ptrs')
-        return win, ccat
-    s0 = (ctypes.c_long * 4)(*feat_f0.stride())
-    s1 = (ctypes.c_long * 4)(*feat_f1.stride())
-    check(_lib.lib().gf_fine_gather(_p(feat_f0), _p(feat_f1), _dt(feat_f0), ctypes.cast(s0, ctypes.c_void_p),
-                                    ctypes.cast(s1, ctypes.c_void_p), feat_f0.shape[2], feat_f0.shape[3], feat_f1.shape[2],
-                                    feat_f1.shape[3], Cf, _p(fc0), _p(fc1), _DTYPES[out_dtype], fc0.shape[1], fc1.shape[1],
-                                    CC, _p(_contig(b_ids)), _p(_contig(i_ids)), _p(_contig(j_ids)), M, int(w0c), int(w1c),
-                                    int(stride), int(window), _p(win), _p(ccat), _stream()), 'gf_fine_gather')
+    # the two entries with strides and extent common to all samples: those of one map (MapBatch: [C,H,W]) or of the batch tensor
+    strides = [feat.map_stride if kind0 is MapBatch else feat.stride() for feat in (feat_f0, feat_f1)]
+    s0, s1 = ((ctypes.c_long * len(st))(*st) for st in strides)
+    geom = (ctypes.cast(s0, ctypes.c_void_p), ctypes.cast(s1, ctypes.c_void_p), *feat_f0.shape[2:], *feat_f1.shape[2:])
+    if kind0 is MapBatch:
+        check(L_.gf_fine_gather_ptrs(_p(feat_f0.table()), _p(feat_f1.table()), len(feat_f0), _dt(feat_f0), min(feat_f0.align, feat_f1.align),
+                                     *geom, *rest), 'gf_fine_gather_ptrs')
+    else:
+        check(L_.gf_fine_gather(_p(feat_f0), _p(feat_f1), _dt(feat_f0), *geom, *rest), 'gf_fine_gather')
     return win, ccat
 
 

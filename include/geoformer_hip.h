@@ -588,7 +588,7 @@ int gf_image_warp_resize(const void* src, int channels, int hs, int ws, long lon
  * Address-table siblings of gf_pos_encode and gf_fine_gather: the maps of the N samples lie in SEPARATE allocations (feature maps
  * kept per image and matched many times) and are read where they lie - no copy into an [N, ...] batch first.  The only difference
  * from the sibling: sample n starts at table[n] (a table of N addresses in DEVICE memory, entries may repeat) instead of x + n * sn.
- * Same kernels (templated on how the base is obtained), same arithmetic, same output bits as the sibling on torch.stack of the maps.
+ * Same kernel, another map source (csrc/gf_maps.h): same arithmetic, same output bits as the sibling on torch.stack of the maps.
  *   *_align  the largest power of two, in bytes, that divides every table entry (the caller built the table on the host and knows;
  *            any smaller power of two is valid and only selects a slower form): the 8-channel vector form of the position encoding
  *            needs 32, the one-wave-per-window form of the gather 16 - the alignment conditions of the siblings, for every entry.
@@ -605,15 +605,15 @@ int gf_fine_gather_ptrs(const void* const* f0_table, const void* const* f1_table
                         void* win_out, void* ccat_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * Ragged siblings of the two address-table entries: the N maps of a batch may differ in EXTENT (images of unequal sizes matched in one
- * padded batch).  The device table holds one record per sample instead of a bare address, and the strides and the extent come from
+ * Ragged siblings of the two address-table entries - same kernel, another map source: the N maps of a batch may differ in EXTENT (images
+ * of unequal sizes matched in one padded batch).  The device table holds one record per sample instead of a bare address, and the strides and the extent come from
  * the record instead of from the arguments.  The maps are anchored at the top left of a common canvas; a canvas position or a window tap
  * outside a sample's own extent reads as ZERO, whatever lies in memory behind the map - nothing outside [0, h) x [0, w) is ever loaded.
  * Output bits: those of gf_pos_encode / gf_fine_gather on the maps zero-padded at the right and bottom to the canvas and then stacked.
  *   gf_pos_encode_ragged   N, C, H, W describe the CANVAS (pe is [H][W][C], out [N][H*W][C]); every record needs h <= H, w <= W (the
  *            caller's promise, like the addresses).  mask_out: NULL, or uint8 [N][H][W] written by the same launch with
  *            (y < h_n && x < w_n) - the padding mask the matching path takes.  N <= 65535 (the sample is a grid dimension).
- *            The form is chosen per sample from its record: 8 channels per lane where sc == 1 and sh, sw are multiples of 8 (and
+ *            The form is chosen per sample from its record (the rule of all three entries, whose strides are the launch's): 8 channels per lane where sc == 1 and sh, sw are multiples of 8 (and
  *            x_align >= 32, C % 8 == 0, pe and out 32-byte aligned), one element per lane for other channels-last maps (sc == 1), and
  *            the 32 x 32 transpose through LDS otherwise (contiguous [C, h, w] maps).
  *   gf_fine_gather_ragged  one table per side, N records each; H0 / W0 / H1 / W1 and the stride arrays of gf_fine_gather_ptrs are gone
