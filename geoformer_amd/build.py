@@ -22,6 +22,7 @@ HOST_CXX = os.environ.get('CXX') or shutil.which('c++') or shutil.which('g++') o
 HOST_FLAGS = ['-O2', '-ffp-contract=off', '-std=c++17', '-fPIC']
 POSE_HOST_LIB = os.path.join(OBJ, 'libpose_host.so')
 WARP_HOST_LIB = os.path.join(OBJ, 'libwarp_host.so')
+KEYPOINT_HOST_LIB = os.path.join(OBJ, 'libkeypoint_host.so')
 
 
 def _headers_digest():
@@ -88,10 +89,18 @@ def build_warp_host(verbose=True):
                            (os.path.join(CSRC, 'warp_spec.h'),), verbose)
 
 
+def build_keypoint_host(verbose=True):
+    """TEST INFRASTRUCTURE and CPU reference: the keypoint consolidation for SfM, serially on the host (csrc/host/keypoint_host.cpp over
+    csrc/keypoint_spec.h, the text k_keypoints.hip compiles for the device).  Only tests and tools/keypoint_probe.py load it."""
+    return _build_host_lib(KEYPOINT_HOST_LIB, 'keypoint_host.stamp', os.path.join(CSRC, 'host', 'keypoint_host.cpp'),
+                           (os.path.join(CSRC, 'keypoint_spec.h'),), verbose)
+
+
 def build(verbose=True, jobs=4):
     os.makedirs(OBJ, exist_ok=True)
     build_pose_host(verbose)
     build_warp_host(verbose)
+    build_keypoint_host(verbose)
     srcs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.hip'))
     hdig = _headers_digest()
     with ThreadPoolExecutor(jobs) as ex:

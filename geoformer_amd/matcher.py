@@ -463,6 +463,61 @@ class GeoFormerMatcher:
 
 
 # ---------------------------------------------------------------------------------------------
+# keypoints and match ids for SfM from pair matches (process_matches_and_keypoints_exporth5 of localize_sfm_helper.py, on the device)
+# ---------------------------------------------------------------------------------------------
+class ConsolidatedMatches(NamedTuple):
+    names: list              # image paths in order of first appearance in the pair list
+    keypoints: list          # per image: [K_i, 2] float32
+    pair_images: np.ndarray  # [P, 2] int32: indices into names
+    matches: list            # per pair: [n_p, 2] int32 keypoint indices (into keypoints[pair_images[p, 0]], keypoints[pair_images[p, 1]])
+
+
+def consolidate_matches(pairs, results, sc_thres=0.25, qt_psize=48, qt_dthres=4, qt_unique=True, device='cuda'):
+    """[(path0, path1), ...] and the tuples match_many returned for them (either return convention: element 0 is the [n, 4] matches,
+    element 3 the scores) -> ConsolidatedMatches: what COLMAP-style triangulation and localisation consume - one keypoint list per image
+    and every match as two keypoint indices.  The reference's process_matches_and_keypoints_exporth5 with its defaults: matches scoring
+    below sc_thres are dropped, keypoints of an image closer than qt_dthres inside one qt_psize cell are merged into their running midpoint
+    (a detector-free matcher never returns the same sub-pixel point twice: without merging every track has length two), and with qt_unique
+    a keypoint keeps only its best match per pair.  qt_psize <= 0 or qt_dthres <= 0: keypoints are merged only where coordinates are equal.
+    Matches are taken as float32 (match_many's upscaled float64 is cast first; the reference stores float32 keypoints anyway).  One upload,
+    ops.consolidate_keypoints on the device, bit-identical to the serial rule (csrc/keypoint_spec.h).  A pair without surviving rows gives
+    [0, 2]; a pair listed twice contributes twice, as in the reference."""
+    pairs = [tuple(p) for p in pairs]
+    if len(pairs) != len(results):
+        raise ValueError(f'consolidate_matches: {len(pairs)} pairs but {len(results)} results')
+    index = {}
+    pair_images = np.array([[index.setdefault(path, len(index)) for path in p] for p in pairs], np.int32).reshape(-1, 2)
+    ms = [np.asarray(r[0], dtype=np.float32).reshape(-1, 4) for r in results]
+    ss = [np.asarray(r[3], dtype=np.float32).reshape(-1) for r in results]
+    if any(len(m) != len(s) for m, s in zip(ms, ss)):
+        raise ValueError('consolidate_matches: a result whose matches and scores differ in length')
+    offsets = np.concatenate([[0], np.cumsum([len(m) for m in ms])]).astype(np.int32)
+    M, P = int(offsets[-1]), len(pairs)
+    # one upload: the four arrays as one block of 32-bit words
+    block = np.concatenate([a.reshape(-1).view(np.int32) for a in (*ms, *ss, offsets, pair_images)])
+    with torch.cuda.device(device):
+        d = torch.from_numpy(block).to(device)
+        matches = d[:4 * M].view(torch.float32).view(M, 4)
+        scores = d[4 * M:5 * M].view(torch.float32)
+        off = d[5 * M:5 * M + P + 1]
+        pim = d[5 * M + P + 1:].view(P, 2)
+        kp, kpo, ids, ido = ops.consolidate_keypoints(matches, scores, off, pim, len(index), sc_thres, qt_psize, qt_dthres, qt_unique)
+        kp, kpo, ids, ido = kp.cpu().numpy(), kpo.cpu().numpy(), ids.cpu().numpy(), ido.cpu().numpy()
+    return ConsolidatedMatches(list(index), [kp[kpo[i]:kpo[i + 1]].copy() for i in range(len(index))], pair_images,
+                               [ids[ido[q]:ido[q + 1]].copy() for q in range(P)])
+
+
+def write_consolidated(out_dir, cm: ConsolidatedMatches):
+    """names.txt (one image path per line, line i = image i), keypoints.npz (k00000, ...: [K_i, 2] float32 per image) and matches.npz
+    (pairs [P, 2] int32 image indices; m00000, ...: [n_p, 2] int32 keypoint indices per pair)."""
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, 'names.txt'), 'w') as f:
+        f.writelines(n + '\n' for n in cm.names)
+    np.savez(os.path.join(out_dir, 'keypoints.npz'), **{f'k{i:05d}': k for i, k in enumerate(cm.keypoints)})
+    np.savez(os.path.join(out_dir, 'matches.npz'), pairs=cm.pair_images, **{f'm{q:05d}': m for q, m in enumerate(cm.matches)})
+
+
+# ---------------------------------------------------------------------------------------------
 # HPatches homography metric
 # ---------------------------------------------------------------------------------------------
 def cal_error_auc(errors, thresholds):
@@ -592,6 +647,7 @@ def eval_hpatches(matcher, data_root, ransac_thres=3, thres=(1, 3, 5, 10), scale
 #   python -m geoformer_amd.matcher match im1 im2 [--ckpt saved_ckpt/geoformer.ckpt] [--out matches.npz] [--preprocess device]
 #   python -m geoformer_amd.matcher hpatches /path/to/hpatches-sequences-release [--ckpt ...] [--preprocess device] [--reuse-features]
 #   python -m geoformer_amd.matcher pairs LIST | --all-pairs DIR  [--out DIR] [--batch B] [--cache-gb G] [--pad [--pad-waste R]]   (no reference counterpart)
+#                                         [--keypoints DIR [--sc-thres S] [--qt-psize P] [--qt-dthres D] [--no-qt-unique]]   (process_matches_and_keypoints_exporth5)
 # ---------------------------------------------------------------------------------------------
 def build_parser():
     """Defaults follow the reference per sub-command: `match` = inference.py:107 (imsize 640, matches scaled back to the
@@ -627,6 +683,14 @@ def build_parser():
                    help='let pairs of unequal shapes share a batch: kept feature maps on a common canvas with padding masks')
     q.add_argument('--pad-waste', type=float, default=None, metavar='R',
                    help=f'with --pad: close a batch before its canvas area exceeds R times its pairs\' own area (default {DEFAULT_PAD_WASTE})')
+    q.add_argument('--keypoints', metavar='DIR', default=None,
+                   help='consolidate the matches for SfM: names.txt, keypoints.npz (one keypoint list per image) and matches.npz (every match as '
+                        'two keypoint indices) under DIR')
+    q.add_argument('--sc-thres', type=float, default=0.25, help='with --keypoints: matches scoring below this are dropped')
+    q.add_argument('--qt-psize', type=float, default=48, help='with --keypoints: cell size of the keypoint quantisation (<= 0: merge equal points only)')
+    q.add_argument('--qt-dthres', type=float, default=4, help='with --keypoints: keypoints of a cell closer than this are merged')
+    q.add_argument('--no-qt-unique', dest='qt_unique', action='store_false',
+                   help='with --keypoints: keep every match of a merged keypoint instead of its best one per pair')
     for p in (h, q):
         p.add_argument('--cache-gb', type=float, default=None,
                        help='byte budget of the feature store in GB: least recently used images are dropped and extracted again when '
@@ -670,6 +734,11 @@ def main(argv=None):
             if args.out:
                 stem = '_'.join(os.path.splitext(os.path.basename(p))[0] for p in (p0, p1))
                 np.savez(os.path.join(args.out, f'{k:05d}_{stem}.npz'), matches=res[0], kpts1=res[1], kpts2=res[2], scores=res[3])
+        if args.keypoints:
+            cm = consolidate_matches(pairs, results, args.sc_thres, args.qt_psize, args.qt_dthres, args.qt_unique, device=matcher.device)
+            write_consolidated(args.keypoints, cm)
+            print(f'{len(cm.names)} images, {sum(len(k) for k in cm.keypoints)} keypoints, {sum(len(m) for m in cm.matches)} matches as keypoint '
+                  f'indices -> {args.keypoints}')
         st = matcher.store
         print(f'{matcher.name}: {len(pairs)} pairs, {sum(len(r[0]) for r in results)} matches, {st.extractions} extractions, {st.hits} store hits')
     elif args.cmd == 'match':

@@ -1017,3 +1017,94 @@ def fine_match_backward(f0, f1, temperature, dconf):
     check(_lib.lib().gf_fine_match_backward(_p(f0), _p(f1), _dt(f0), M, WW, C, float(temperature), _p(dconf), _p(df[0]), _p(df[1]), _stream()),
           'gf_fine_match_backward')
     return df[0], df[1]
+
+
+# ---------------------------------------------------------------------------------------------
+# keypoint consolidation for SfM (csrc/k_keypoints.hip over csrc/keypoint_spec.h)
+# ---------------------------------------------------------------------------------------------
+KP_FLAG_COORD_RANGE, KP_FLAG_IMAGE_RANGE = 1, 2        # keypoint_spec.h KP_FLAG_*: bits of counts[0]
+
+
+def consolidate_keypoints(matches, scores, pair_offsets, pair_images, n_images, sc_thres=0.25, psize=48.0, dthres=4.0, unique=True):
+    """Pair matches -> one keypoint list per image and every match as a pair of keypoint indices, on the device: the reference's
+    process_matches_and_keypoints_exporth5 / matches_to_keypoint_ids (score filter, quantize_keypoints or compute_keypoints, the uniqueness
+    filter), bit for bit.  Device tensors: matches [M,4] (x0, y0, x1, y1; cast to fp32 first, as the reference stores them), scores [M],
+    pair_offsets [P+1] (ascending, first 0, last M), pair_images [P,2] (image index of each side; a pair listed twice contributes twice).
+    Returns (keypoints fp32 [K,2] image-major, kp_offsets int32 [n_images+1], ids int32 [M',2] per-image keypoint indices in row order,
+    ids_offsets int32 [P+1]).  psize <= 0 or dthres <= 0: the exact mode (equal coordinates share a keypoint; no filter, as in the reference).
+    Rows with a score below sc_thres, a NaN score or a non-finite coordinate are dropped (the reference would carry NaN through its
+    dictionaries).  Supported: n_images <= 524288; quantised mode: psize > 2 and |coordinates| <= 2^22 - a larger coordinate or an image
+    index outside [0, n_images) raises after the call's one device-to-host read (the output sizes and the status word), nothing wraps.
+    Between the kernels, the order-preserving plumbing is torch's: one stable sort by group key and three scans."""
+    _need_cuda(matches, scores, pair_offsets, pair_images)
+    dev = matches.device
+    M, P, n_images = int(matches.shape[0]), int(pair_images.shape[0]), int(n_images)
+    if matches.shape != (M, 4) or scores.shape != (M,) or pair_offsets.shape != (P + 1,) or pair_images.shape != (P, 2):
+        raise ValueError('consolidate_keypoints: matches [M,4], scores [M], pair_offsets [P+1], pair_images [P,2]')
+    m, sc = _contig(matches.to(torch.float32)), _contig(scores.to(torch.float32))
+    off, pim = _contig(pair_offsets.to(torch.int32)), _contig(pair_images.to(torch.int32))
+    psize, dthres = float(psize), float(dthres)
+    quant = psize > 0 and dthres > 0
+    N = 2 * M
+    L_ = _lib.lib()
+
+    def i32(*shape):
+        return torch.empty(*shape, dtype=torch.int32, device=dev)
+    counts = i32(8)
+    keys = torch.empty(N, dtype=torch.int64, device=dev)
+    keys2 = None if quant else torch.empty(N, dtype=torch.int64, device=dev)
+    pts = torch.empty(N, 2, dtype=torch.float32, device=dev)
+    pseg, seg_begin = i32(N), i32(N)
+    check(L_.gf_keypoint_keys(_p(m), _p(sc), _p(off), _p(pim), P, M, n_images, float(sc_thres), psize, dthres, _p(keys), _p(keys2), _p(pts),
+                              _p(pseg), _p(seg_begin), _p(counts), _stream()), 'gf_keypoint_keys')
+    if M == 0:
+        return (torch.zeros(0, 2, dtype=torch.float32, device=dev), torch.zeros(n_images + 1, dtype=torch.int32, device=dev),
+                torch.zeros(0, 2, dtype=torch.int32, device=dev), torch.zeros(P + 1, dtype=torch.int32, device=dev))
+    if n_images < 1:
+        raise ValueError('consolidate_keypoints: rows but no images')
+    # grouping: a stable sort keeps arrival order inside a group (exact mode: least significant key first)
+    if quant:
+        order = torch.sort(keys, stable=True).indices
+    else:
+        o2 = torch.sort(keys2, stable=True).indices
+        order = o2[torch.sort(keys[o2], stable=True).indices]
+    head = i32(N)
+    check(L_.gf_keypoint_heads(_p(keys), _p(keys2), _p(order), M, _p(head), _stream()), 'gf_keypoint_heads')
+    group_scan = torch.cumsum(head, 0, dtype=torch.int32)
+    ws = _ws.get('keypoints', L_.gf_keypoint_workspace_bytes(M), dev)
+    owner, slot, creator = i32(N), i32(N), i32(N)
+    cxy = torch.empty(N, 2, dtype=torch.float32, device=dev)
+    check(L_.gf_keypoint_walk(_p(keys), _p(order), _p(head), _p(group_scan), _p(pts), _p(seg_begin), M, psize, dthres, _p(owner), _p(slot),
+                              _p(creator), _p(cxy), _p(counts), _p(ws), ws.numel(), _stream()), 'gf_keypoint_walk')
+    # keypoint ranks: a creator's id is its rank among its image's creators in arrival order.  Arrival order is segment (pair, side) major and a
+    # segment lies in one image, so: scan the creator flags, count per segment, order the segments by image (stably), scan again - 2 P numbers.
+    creator_scan = torch.cumsum(creator, 0, dtype=torch.int32)
+    cx = torch.cat([creator_scan.new_zeros(1), creator_scan]).long()
+    o64 = off.long()
+    n = o64[1:] - o64[:-1]
+    seg_b = torch.stack([2 * o64[:-1], 2 * o64[:-1] + n], 1).reshape(-1)
+    seg_e = torch.stack([2 * o64[:-1] + n, 2 * o64[1:]], 1).reshape(-1)
+    seg_cnt = cx[seg_e] - cx[seg_b]
+    simg = pim.reshape(-1).long().clamp(0, n_images - 1)            # (a pair with an index out of range has no creators; the status word reports it)
+    so = torch.sort(simg, stable=True).indices
+    csum = torch.cat([seg_cnt.new_zeros(1), torch.cumsum(seg_cnt[so], 0)])
+    seg_base = torch.empty_like(seg_cnt)
+    seg_base[so] = csum[:-1]
+    seg_adj = (seg_base - cx[seg_b]).to(torch.int32)
+    kp_offsets = csum[torch.searchsorted(simg[so], torch.arange(n_images + 1, device=dev))].to(torch.int32)
+    keep = i32(M)
+    check(L_.gf_keypoint_filter(_p(sc), _p(off), P, M, _p(owner), _p(slot), int(bool(unique) and quant), _p(keep), _p(ws), ws.numel(), _stream()),
+          'gf_keypoint_filter')
+    keep_scan = torch.cumsum(keep, 0, dtype=torch.int32)
+    keypoints = torch.empty(N, 2, dtype=torch.float32, device=dev)
+    ids = i32(M, 2)
+    ids_offsets = i32(P + 1)
+    check(L_.gf_keypoint_emit(_p(creator), _p(creator_scan), _p(pseg), _p(seg_adj), _p(cxy), _p(keep), _p(keep_scan), _p(off), _p(pim), P, M,
+                              _p(owner), _p(kp_offsets), _p(keypoints), _p(ids), _p(ids_offsets), _p(counts), _stream()), 'gf_keypoint_emit')
+    c = counts.cpu()                                                # the one device-to-host read: status bits, K, M'
+    flags, K, rows = int(c[0]), int(c[4]), int(c[5])
+    if flags & KP_FLAG_IMAGE_RANGE:
+        raise _lib.GeoFormerHipError(f'consolidate_keypoints: pair_images holds an index outside [0, {n_images})')
+    if flags & KP_FLAG_COORD_RANGE:
+        raise _lib.GeoFormerHipError('consolidate_keypoints: a coordinate lies outside the supported +-2^22 of the quantised mode')
+    return keypoints[:K], kp_offsets, ids[:rows], ids_offsets

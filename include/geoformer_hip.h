@@ -38,7 +38,8 @@ typedef enum { GF_F32 = 0, GF_F16 = 1, GF_BF16 = 2 } gf_dtype;
 /* 4 (round 4): the fragment stream of gf_conv3x3_nhwc deals the output channels differently (fused.py:pack_conv3x3_stream: a stream packed for
  * version 3 gives wrong channels) and GF_CONV_PAD16 now states that channels 196 .. 223 are padding; new: GF_CONV_S2, gf_lateral_upsample_add_nhwc. */
 /* Still 4 with gf_pos_encode_ptrs / gf_fine_gather_ptrs and gf_pos_encode_ragged / gf_fine_gather_ragged (with gf_map_record): entries appended at
- * the end change no existing one; a binding that needs them fails at load on the missing symbol (geoformer_amd/_lib.py binds every name). */
+ * the end change no existing one; a binding that needs them fails at load on the missing symbol (geoformer_amd/_lib.py binds every name).
+ * Likewise with the gf_keypoint_* entries. */
 #define GF_ABI_VERSION 4
 int gf_abi_version(void);
 const char* gf_last_error(void);
@@ -634,6 +635,52 @@ int gf_fine_gather_ragged(const gf_map_record* f0_table, const gf_map_record* f1
                           const void* feat_c0, const void* feat_c1, int dtype, int L, int S, int CC, const int64_t* b_ids,
                           const int64_t* i_ids, const int64_t* j_ids, int M, int w0c, int w1c, int stride, int window,
                           void* win_out, void* ccat_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Keypoint consolidation for SfM: pair matches -> one keypoint list per image + every match as a pair of keypoint indices
+ * replaces quantize_keypoints, compute_keypoints, get_unique_matches_ids, matches_to_keypoint_ids and the score filter of
+ *          process_matches_and_keypoints_exporth5 (eval_tool/immatch/utils/localize_sfm_helper.py:149-230, :353-355, :378-413)
+ *
+ * The rule (point order, cell, one point against a cell's centres, the filter's winner) is geoformer_amd/csrc/keypoint_spec.h; the serial host
+ * form of the whole is csrc/host/keypoint_host.cpp, and the device path gives its bits.  psize <= 0 or dthres <= 0 selects the exact mode
+ * (equal coordinates share a keypoint, no filter).  Inputs are fp32: matches [M][4] (x0, y0, x1, y1), scores [M], pair_offsets int32 [P + 1]
+ * (ascending, first 0, last M: the rows of pair q), pair_images int32 [P][2].  M <= 2^30 - 1.  A row is dropped when its score is below
+ * sc_thres or NaN, or a coordinate is not finite.
+ *   SUPPORTED RANGES, checked BEFORE anything is launched (GF_ERR_INVALID_ARGUMENT): n_images <= 524288 (19 key bits); in the quantised mode
+ *   psize finite and > 2, so that the cell index floor(c / psize) of any |c| <= 2^22 fits 22 signed bits.  What only the data can break is
+ *   reported, never wrapped: a surviving row with a |coordinate| > 2^22 (quantised mode) sets bit 0 of counts[0] and is dropped; a pair whose
+ *   image index lies outside [0, n_images) sets bit 1 and loses its rows.
+ * The stages, each only enqueuing on `stream`; N = 2 M points in ARRIVAL order (pair, side, row).  The caller owns every buffer and runs the
+ * three order-preserving primitives between the stages (a stable sort and two inclusive scans - any implementation):
+ *   gf_keypoint_keys     clears counts (int32 [8]: [0] status bits, [4] K keypoints, [5] M' rows - valid after gf_keypoint_emit; the rest is
+ *                        internal) and writes keys int64 [N] (dropped points: INT64_MAX), keys2 int64 [N] (exact mode only; may be NULL
+ *                        otherwise), pts fp32 [N][2], pseg int32 [N] (2 * pair + side), seg_begin int32 [N]
+ *   -> order int64 [N] = the permutation of a STABLE ascending sort by keys (exact mode: by (keys, keys2))
+ *   gf_keypoint_heads    head int32 [N]: 1 at the sorted positions where a group starts          -> group_scan = inclusive scan of head
+ *   gf_keypoint_walk     owner int32 [N] (arrival index of the point that created the point's keypoint; -1: dropped), slot int32 [N],
+ *                        creator int32 [N] (0 / 1), cxy fp32 [N][2] (final coordinates, at the creating points)
+ *   -> creator_scan = inclusive scan of creator (arrival order); seg_adj int32 [2 P]: for segment s = 2 * pair + side, (keypoints of all
+ *      lower images + keypoints created for its image by earlier segments) - (creators before the segment's first point); kp_offsets
+ *      int32 [n_images + 1]
+ *   gf_keypoint_filter   keep int32 [M]: surviving rows that win both of their keypoints within their pair (unique == 0: every surviving
+ *                        row).  The winner of a keypoint: the highest score, between equal scores the lower row.  -> keep_scan = inclusive scan
+ *   gf_keypoint_emit     keypoints fp32 [K][2] image-major (room for N rows), ids int32 [M'][2] in row order (room for M rows),
+ *                        pair_offsets_out int32 [P + 1], counts[4], counts[5]
+ * workspace: gf_keypoint_workspace_bytes(M) bytes, the SAME buffer for gf_keypoint_walk and gf_keypoint_filter.  Bit-identical from run to run.
+ * ------------------------------------------------------------------------------------------ */
+size_t gf_keypoint_workspace_bytes(int M);
+int gf_keypoint_keys(const float* matches, const float* scores, const int* pair_offsets, const int* pair_images, int P, int M,
+                     int n_images, float sc_thres, float psize, float dthres, long long* keys, long long* keys2, float* pts,
+                     int* pseg, int* seg_begin, int* counts, void* stream);
+int gf_keypoint_heads(const long long* keys, const long long* keys2, const long long* order, int M, int* head, void* stream);
+int gf_keypoint_walk(const long long* keys, const long long* order, const int* head, const int* group_scan, const float* pts,
+                     const int* seg_begin, int M, float psize, float dthres, int* owner, int* slot, int* creator, float* cxy,
+                     int* counts, void* workspace, size_t workspace_bytes, void* stream);
+int gf_keypoint_filter(const float* scores, const int* pair_offsets, int P, int M, const int* owner, const int* slot, int unique,
+                       int* keep, void* workspace, size_t workspace_bytes, void* stream);
+int gf_keypoint_emit(const int* creator, const int* creator_scan, const int* pseg, const int* seg_adj, const float* cxy, const int* keep,
+                     const int* keep_scan, const int* pair_offsets, const int* pair_images, int P, int M, const int* owner,
+                     const int* kp_offsets, float* keypoints, int* ids, int* pair_offsets_out, int* counts, void* stream);
 
 #ifdef __cplusplus
 }
