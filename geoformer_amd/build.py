@@ -23,6 +23,7 @@ HOST_FLAGS = ['-O2', '-ffp-contract=off', '-std=c++17', '-fPIC']
 POSE_HOST_LIB = os.path.join(OBJ, 'libpose_host.so')
 WARP_HOST_LIB = os.path.join(OBJ, 'libwarp_host.so')
 KEYPOINT_HOST_LIB = os.path.join(OBJ, 'libkeypoint_host.so')
+FUND_HOST_LIB = os.path.join(OBJ, 'libfund_host.so')
 
 
 def _headers_digest():
@@ -79,7 +80,7 @@ def build_pose_host(verbose=True):
     """TEST INFRASTRUCTURE: the serial host form of the essential-matrix RANSAC (csrc/host/pose_host.cpp over csrc/pose_solver.h, the
     text k_pose.hip compiles for the device), built by the host C++ compiler without offload.  Only tests load it."""
     return _build_host_lib(POSE_HOST_LIB, 'pose_host.stamp', os.path.join(CSRC, 'host', 'pose_host.cpp'),
-                           (os.path.join(CSRC, 'pose_solver.h'), os.path.join(CSRC, 'gf_hash.h')), verbose)
+                           (os.path.join(CSRC, 'pose_solver.h'), os.path.join(CSRC, 'solver_common.h'), os.path.join(CSRC, 'gf_hash.h')), verbose)
 
 
 def build_warp_host(verbose=True):
@@ -96,11 +97,19 @@ def build_keypoint_host(verbose=True):
                            (os.path.join(CSRC, 'keypoint_spec.h'),), verbose)
 
 
+def build_fund_host(verbose=True):
+    """TEST INFRASTRUCTURE: the serial host form of the fundamental-matrix RANSAC (csrc/host/fund_host.cpp over csrc/fund_solver.h, the
+    text k_fundamental.hip compiles for the device).  Only tests load it."""
+    return _build_host_lib(FUND_HOST_LIB, 'fund_host.stamp', os.path.join(CSRC, 'host', 'fund_host.cpp'),
+                           tuple(os.path.join(CSRC, h) for h in ('fund_solver.h', 'solver_common.h', 'keypoint_spec.h', 'gf_hash.h')), verbose)
+
+
 def build(verbose=True, jobs=4):
     os.makedirs(OBJ, exist_ok=True)
     build_pose_host(verbose)
     build_warp_host(verbose)
     build_keypoint_host(verbose)
+    build_fund_host(verbose)
     srcs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.hip'))
     hdig = _headers_digest()
     with ThreadPoolExecutor(jobs) as ex:

@@ -1,0 +1,100 @@
+// TEST INFRASTRUCTURE: the serial host form of the fundamental-matrix RANSAC of k_fundamental.hip, compiled from the same fund_solver.h
+// by the host C++ compiler (geoformer_amd/build.py: -O2 -ffp-contract=off, no offload) into csrc/_obj/libfund_host.so.  The tests compare
+// the device against it bit for bit; nothing in the package loads it.
+#include <stdint.h>
+#include <string.h>
+
+#include <vector>
+
+#include "../fund_solver.h"
+
+extern "C" {
+
+// x0, x1 [7][2] fp64 pixels, norm [6] (cx, cy, s of image 0, then of image 1) -> F_out [3][9]; returns the number of solutions
+int gf_fund_host_seven_point(const double* x0, const double* x1, const double* norm, double* F_out) {
+    double a[7][2], b[7][2], nm[6], ws[FS_WS_DOUBLES];
+    for (int i = 0; i < 7; ++i) { a[i][0] = x0[2 * i]; a[i][1] = x0[2 * i + 1]; b[i][0] = x1[2 * i]; b[i][1] = x1[2 * i + 1]; }
+    for (int i = 0; i < 6; ++i) nm[i] = norm[i];
+    for (int i = 0; i < FS_WS_DOUBLES; ++i) ws[i] = 0.0;
+    const GsWs w{ws, 1};
+    const int n = fs_seven_point(a, b, nm, w);
+    for (int k = 0; k < 9 * n; ++k) F_out[k] = ws[FS_OFF_F + k];
+    return n;
+}
+
+// the singular members of the pencil of F1, F2 [9] (no conditioning, no change of coordinates) -> F_out [3][9]; returns their number
+int gf_fund_host_pencil(const double* F1, const double* F2, double* F_out) {
+    double ws[FS_WS_DOUBLES];
+    for (int i = 0; i < FS_WS_DOUBLES; ++i) ws[i] = 0.0;
+    for (int k = 0; k < 9; ++k) { ws[FS_OFF_BASIS + k] = F1[k]; ws[FS_OFF_BASIS + 9 + k] = F2[k]; }
+    const GsWs w{ws, 1};
+    const int n = fs_pencil(w);
+    for (int k = 0; k < 9 * n; ++k) F_out[k] = ws[FS_OFF_F + k];
+    return n;
+}
+
+// One pair: matches [n][4] fp32 pixels, scores [n] or NULL.  Outputs as gf_fundamental_ransac writes them for pair `sample` of a launch:
+// F [9], hyp [2] (hypothesis, root; -1 when not valid), n_inliers [1], mask [n].  Returns valid (0 / 1), or -1 (GF_ERR_INVALID_ARGUMENT)
+// for arguments the device entry point rejects.
+int gf_fund_host_ransac(const float* matches, const float* scores, int n, float sc_thres, double pixel_thr, int iters, uint32_t seed,
+                        uint32_t sample, double* F_out, int32_t* hyp_out, int32_t* n_inliers, uint8_t* mask) {
+    if (iters <= 0 || iters % FS_HYP_PER_WG != 0 || n < 0 || !(pixel_thr > 0.0)) return -1;
+    for (int k = 0; k < 9; ++k) F_out[k] = 0.0;
+    hyp_out[0] = hyp_out[1] = -1;
+    *n_inliers = 0;
+    for (int i = 0; i < n; ++i) mask[i] = 0;
+    std::vector<int32_t> rows;
+    float box[8] = {0, 0, 0, 0, 0, 0, 0, 0};          // min, max of x0, y0, x1, y1
+    for (int i = 0; i < n; ++i) {
+        const float* m = matches + 4 * (size_t)i;
+        if (!fs_row_valid(m, scores, i, sc_thres)) continue;
+        for (int k = 0; k < 4; ++k) {
+            if (rows.empty() || m[k] < box[2 * k]) box[2 * k] = m[k];
+            if (rows.empty() || m[k] > box[2 * k + 1]) box[2 * k + 1] = m[k];
+        }
+        rows.push_back(i);
+    }
+    const int cnt = (int)rows.size();
+    if (cnt < FS_MIN_MATCHES) return 0;
+    double nm[6];
+    const int ok0 = fs_box_norm(box[0], box[1], box[2], box[3], nm), ok1 = fs_box_norm(box[4], box[5], box[6], box[7], nm + 3);
+    if (!ok0 || !ok1) return 0;
+    const double thr2 = pixel_thr * pixel_thr;
+    double ws[FS_WS_DOUBLES];
+    const GsWs w{ws, 1};
+    int best_cnt = -1, best_t = -1, best_r = -1;
+    double best[9];
+    for (int t = 0; t < iters; ++t) {
+        int idx[7];
+        if (!fs_draw7(seed, sample, (uint32_t)t, cnt, matches, rows.data(), idx)) continue;
+        double x0[7][2], x1[7][2];
+        for (int k = 0; k < 7; ++k) {
+            const float* m = matches + 4 * (size_t)rows[idx[k]];
+            x0[k][0] = (double)m[0]; x0[k][1] = (double)m[1]; x1[k][0] = (double)m[2]; x1[k][1] = (double)m[3];
+        }
+        const int nr = fs_seven_point(x0, x1, nm, w);
+        for (int r = 0; r < nr; ++r) {
+            double F[9];
+            for (int k = 0; k < 9; ++k) F[k] = ws[FS_OFF_F + 9 * r + k];
+            int c = 0;
+            for (int i = 0; i < cnt; ++i) c += fs_inlier(F, matches + 4 * (size_t)rows[i], thr2);
+            if (c > best_cnt) {                       // most inliers, then smallest hypothesis, then smallest root
+                best_cnt = c; best_t = t; best_r = r;
+                for (int k = 0; k < 9; ++k) best[k] = F[k];
+            }
+        }
+    }
+    if (best_cnt < 0) return 0;
+    int nin = 0;
+    for (int i = 0; i < cnt; ++i) {
+        const int in = fs_inlier(best, matches + 4 * (size_t)rows[i], thr2);
+        mask[rows[i]] = (uint8_t)in;
+        nin += in;
+    }
+    for (int k = 0; k < 9; ++k) F_out[k] = best[k];
+    hyp_out[0] = best_t; hyp_out[1] = best_r;
+    *n_inliers = nin;
+    return 1;
+}
+
+}   // extern "C"

@@ -25,20 +25,13 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "gf_hash.h"
+#include "solver_common.h"
 
-#if defined(__HIPCC__)
-#define PS_HD __host__ __device__ inline
-#define PS_HD_MEMBER __host__ __device__
-#else
-#define PS_HD static inline
-#define PS_HD_MEMBER
-#endif
+#define PS_HD GS_HD
+#define PS_HD_MEMBER GS_HD_MEMBER
+#define PS_UNROLL GS_UNROLL
 #if defined(__clang__)
 #pragma clang fp contract(off)
-#define PS_UNROLL _Pragma("unroll")
-#else
-#define PS_UNROLL
 #endif
 
 #define PS_MAX_ROOTS 10
@@ -63,16 +56,9 @@
 #define PS_OFF_R1 88              /* [12] roots being found */
 #define PS_OFF_E 100              /* [10][9] the solutions, Frobenius norm 1 */
 
-struct PsWs {
-    double* p;
-    int s;
-    PS_HD_MEMBER double& operator()(int i) const { return p[(long)i * s]; }
-};
+typedef GsWs PsWs;
 
-PS_HD double ps_abs_or_inf(double v) {            // |v|, a NaN counted as +inf: it wins every pivot search and fails the solve
-    const double a = fabs(v);
-    return a == a ? a : (double)INFINITY;
-}
+PS_HD double ps_abs_or_inf(double v) { return gs_abs_or_inf(v); }
 
 // ---- monomials: exponents (a, b, c) of x, y, z packed as 16 a + 4 b + c (no carries up to degree 3)
 PS_HD int ps_key1(int i) { return i == 0 ? 16 : i == 1 ? 4 : i == 2 ? 1 : 0; }                      // x y z 1
@@ -116,8 +102,7 @@ PS_HD void ps_mul21(double (&d)[20], const double (&a)[10], const double (&b)[4]
     }
 }
 
-// ---- null space of the 5x9 epipolar system: Gauss-Jordan with full pivoting, columns swapped in place (perm: nibble j = the
-// original column now at position j).  Basis vector k has 1 at free column 5 + k and -A[i][5 + k] at pivot column i.
+// ---- null space of the 5x9 epipolar system: Gauss-Jordan with full pivoting (solver_common.h: gs_eliminate9, gs_null_basis)
 PS_HD int ps_nullspace(const double (&x0)[5][2], const double (&x1)[5][2], const PsWs& w) {
     for (int r = 0; r < 5; ++r) {
         const double a = x0[r][0], b = x0[r][1], u = x1[r][0], v = x1[r][1];
@@ -125,37 +110,9 @@ PS_HD int ps_nullspace(const double (&x0)[5][2], const double (&x1)[5][2], const
         w(9 * r + 3) = v * a; w(9 * r + 4) = v * b; w(9 * r + 5) = v;
         w(9 * r + 6) = a; w(9 * r + 7) = b; w(9 * r + 8) = 1.0;
     }
-    unsigned long long perm = 0x876543210ull;
-    for (int c = 0; c < 5; ++c) {
-        int pr = c, pc = c;
-        double best = -1.0;
-        for (int r = c; r < 5; ++r)
-            for (int j = c; j < 9; ++j) {
-                const double v = ps_abs_or_inf(w(9 * r + j));
-                if (v > best) { best = v; pr = r; pc = j; }
-            }
-        if (!(best > 1e-12) || best == (double)INFINITY) return 0;
-        if (pr != c)
-            for (int j = 0; j < 9; ++j) { const double tmp = w(9 * c + j); w(9 * c + j) = w(9 * pr + j); w(9 * pr + j) = tmp; }
-        if (pc != c) {
-            for (int r = 0; r < 5; ++r) { const double tmp = w(9 * r + c); w(9 * r + c) = w(9 * r + pc); w(9 * r + pc) = tmp; }
-            const unsigned long long nc = (perm >> (4 * c)) & 15ull, np = (perm >> (4 * pc)) & 15ull;
-            perm = (perm & ~(15ull << (4 * c)) & ~(15ull << (4 * pc))) | (np << (4 * c)) | (nc << (4 * pc));
-        }
-        const double inv = 1.0 / w(9 * c + c);
-        for (int j = c; j < 9; ++j) w(9 * c + j) = w(9 * c + j) * inv;
-        for (int r = 0; r < 5; ++r) {
-            if (r == c) continue;
-            const double f = w(9 * r + c);
-            if (f != 0.0)
-                for (int j = c; j < 9; ++j) w(9 * r + j) = w(9 * r + j) - f * w(9 * c + j);
-        }
-    }
-    for (int k = 0; k < 4; ++k) {
-        for (int j = 0; j < 9; ++j) w(PS_OFF_BASIS + 9 * k + j) = 0.0;
-        w(PS_OFF_BASIS + 9 * k + (int)((perm >> (4 * (5 + k))) & 15ull)) = 1.0;
-        for (int i = 0; i < 5; ++i) w(PS_OFF_BASIS + 9 * k + (int)((perm >> (4 * i)) & 15ull)) = -w(9 * i + 5 + k);
-    }
+    unsigned long long perm;
+    if (!gs_eliminate9<5>(w, perm)) return 0;
+    gs_null_basis<5>(w, perm, PS_OFF_BASIS);
     // Mix the four vectors by the orthogonal 4x4 Hadamard matrix / 2.  Small rotations make E nearly skew-symmetric, and when the free
     // columns hold a pair E[i][j], E[j][i] EVERY solution has z = E[i][j] / E[j][i] near -1: ten roots in a cluster of radius rho, whose
     // expanded polynomial cancels by rho^-10.  In the mixed basis no coordinate ratio is tied to a pair of entries of E.
@@ -291,75 +248,10 @@ PS_HD void ps_detpoly(const PsWs& w) {
     ps_polymul(w, PS_OFF_P, r0 + 8, 5, t3, 7, false);
 }
 
-PS_HD double ps_horner(const double (&q)[11], double x) {
-    double s = q[10];
-    PS_UNROLL
-    for (int k = 9; k >= 0; --k) s = s * x + q[k];
-    return s;
-}
-
 // real roots of the polynomial at PS_OFF_P, ascending, into PS_OFF_R0; returns their number (0 when the polynomial is not of
 // degree 10 in finite numbers)
 PS_HD int ps_real_roots(const PsWs& w) {
-    const double lead = w(PS_OFF_P + 10);
-    double big = 0.0;
-    for (int k = 0; k < 10; ++k) {
-        const double v = ps_abs_or_inf(w(PS_OFF_P + k));
-        big = v > big ? v : big;
-    }
-    if (!(fabs(lead) > 0.0)) return 0;
-    const double bound = 1.0 + big / fabs(lead);                   // Cauchy
-    if (!(bound < (double)INFINITY)) return 0;
-    int nprev = 0;
-    for (int m = 1; m <= 10; ++m) {
-        const int s = 10 - m;                                      // q = the s-th derivative of p, degree m
-        double q[11];
-        PS_UNROLL
-        for (int i = 0; i <= 10; ++i) {
-            double c = 0.0;
-            if (i <= m) {
-                c = w(PS_OFF_P + i + s);
-                for (int t = 1; t <= s; ++t) c = c * (double)(i + t);
-            }
-            q[i] = c;
-        }
-        const int iters = m == 10 ? PS_BISECT_TOP : PS_BISECT_LOW;
-        int nnew = 0;
-        double lo = -bound, flo = ps_horner(q, lo);
-        for (int j = 0; j <= nprev; ++j) {
-            const double hi = j < nprev ? w(PS_OFF_R0 + j) : bound;
-            const double fhi = ps_horner(q, hi);
-            if ((flo > 0.0) != (fhi > 0.0)) {
-                double a = lo, b = hi;
-                for (int it = 0; it < iters; ++it) {
-                    const double mid = 0.5 * (a + b);
-                    const double fm = ps_horner(q, mid);
-                    if ((fm > 0.0) == (flo > 0.0)) a = mid; else b = mid;
-                }
-                w(PS_OFF_R1 + nnew) = 0.5 * (a + b);
-                ++nnew;
-            }
-            lo = hi; flo = fhi;
-        }
-        for (int j = 0; j < nnew; ++j) w(PS_OFF_R0 + j) = w(PS_OFF_R1 + j);
-        nprev = nnew;
-        if (m == 10) {
-            double dq[11];
-            PS_UNROLL
-            for (int i = 0; i < 10; ++i) dq[i] = q[i + 1] * (double)(i + 1);
-            dq[10] = 0.0;
-            for (int j = 0; j < nnew; ++j) {
-                double z = w(PS_OFF_R0 + j), f = ps_horner(q, z);
-                for (int it = 0; it < PS_NEWTON; ++it) {
-                    const double zn = z - f / ps_horner(dq, z);
-                    const double fn = ps_horner(q, zn);
-                    if (fabs(fn) < fabs(f)) { z = zn; f = fn; }     // a NaN or a worse step is not taken
-                }
-                w(PS_OFF_R0 + j) = z;
-            }
-        }
-    }
-    return nprev;
+    return gs_real_roots<10>(w, PS_OFF_P, PS_OFF_R0, PS_OFF_R1, PS_BISECT_LOW, PS_BISECT_TOP, PS_NEWTON);
 }
 
 // residuals of the ten cubic constraints at a numeric E: c[0..8] = 2 E E^T E - tr(E E^T) E, c[9] = det E

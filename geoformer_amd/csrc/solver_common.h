@@ -1,0 +1,155 @@
+// What the minimal solvers share (pose_solver.h: five points, essential matrix; fund_solver.h: seven points, fundamental matrix), stated
+// once for the device and the host.  Plain C++ in fp64 with contraction off, only + - * / sqrt, fabs and comparisons, so a host build and
+// gfx950 agree bit for bit.  Everything indexed at run time is reached through GsWs (element i at p[i * stride]): the caller decides where
+// it lives - a local array on the host, an LDS tile interleaved across the lanes of a workgroup on the device.
+//
+//   gs_eliminate9<R>   Gauss-Jordan with full pivoting on the R x 9 epipolar system at the start of the workspace, columns swapped in
+//                      place (perm: nibble j = the original column now at position j).
+//   gs_null_basis<R>   the 9 - R null vectors of the eliminated system: vector k has 1 at free column R + k, -A[i][R + k] at pivot column i.
+//   gs_real_roots<D>   real roots of a polynomial of degree D without an eigen-solver: the roots of the k-th derivative separate those of
+//                      the (k-1)-th, so the chain p^(D-1) (linear) .. p^(0) is walked upwards, every sign change between neighbouring
+//                      critical points bisected a FIXED number of times, then guarded Newton steps on p itself.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+
+#include "gf_hash.h"
+
+#if defined(__HIPCC__)
+#define GS_HD __host__ __device__ inline
+#define GS_HD_MEMBER __host__ __device__
+#else
+#define GS_HD static inline
+#define GS_HD_MEMBER
+#endif
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#define GS_UNROLL _Pragma("unroll")
+#else
+#define GS_UNROLL
+#endif
+
+struct GsWs {
+    double* p;
+    int s;
+    GS_HD_MEMBER double& operator()(int i) const { return p[(long)i * s]; }
+};
+
+GS_HD double gs_abs_or_inf(double v) {            // |v|, a NaN counted as +inf: it wins every pivot search and fails the solve
+    const double a = fabs(v);
+    return a == a ? a : (double)INFINITY;
+}
+
+// rows 0 .. R - 1 of 9 doubles each at w(9 r + j).  Returns 0 for a rank-deficient or non-finite system.
+template <int R>
+GS_HD int gs_eliminate9(const GsWs& w, unsigned long long& perm) {
+    perm = 0x876543210ull;
+    for (int c = 0; c < R; ++c) {
+        int pr = c, pc = c;
+        double best = -1.0;
+        for (int r = c; r < R; ++r)
+            for (int j = c; j < 9; ++j) {
+                const double v = gs_abs_or_inf(w(9 * r + j));
+                if (v > best) { best = v; pr = r; pc = j; }
+            }
+        if (!(best > 1e-12) || best == (double)INFINITY) return 0;
+        if (pr != c)
+            for (int j = 0; j < 9; ++j) { const double tmp = w(9 * c + j); w(9 * c + j) = w(9 * pr + j); w(9 * pr + j) = tmp; }
+        if (pc != c) {
+            for (int r = 0; r < R; ++r) { const double tmp = w(9 * r + c); w(9 * r + c) = w(9 * r + pc); w(9 * r + pc) = tmp; }
+            const unsigned long long nc = (perm >> (4 * c)) & 15ull, np = (perm >> (4 * pc)) & 15ull;
+            perm = (perm & ~(15ull << (4 * c)) & ~(15ull << (4 * pc))) | (np << (4 * c)) | (nc << (4 * pc));
+        }
+        const double inv = 1.0 / w(9 * c + c);
+        for (int j = c; j < 9; ++j) w(9 * c + j) = w(9 * c + j) * inv;
+        for (int r = 0; r < R; ++r) {
+            if (r == c) continue;
+            const double f = w(9 * r + c);
+            if (f != 0.0)
+                for (int j = c; j < 9; ++j) w(9 * r + j) = w(9 * r + j) - f * w(9 * c + j);
+        }
+    }
+    return 1;
+}
+
+template <int R>
+GS_HD void gs_null_basis(const GsWs& w, unsigned long long perm, int off_basis) {
+    for (int k = 0; k < 9 - R; ++k) {
+        for (int j = 0; j < 9; ++j) w(off_basis + 9 * k + j) = 0.0;
+        w(off_basis + 9 * k + (int)((perm >> (4 * (R + k))) & 15ull)) = 1.0;
+        for (int i = 0; i < R; ++i) w(off_basis + 9 * k + (int)((perm >> (4 * i)) & 15ull)) = -w(9 * i + R + k);
+    }
+}
+
+template <int D>
+GS_HD double gs_horner(const double (&q)[D + 1], double x) {
+    double s = q[D];
+    GS_UNROLL
+    for (int k = D - 1; k >= 0; --k) s = s * x + q[k];
+    return s;
+}
+
+// real roots of the polynomial at off_p (D + 1 coefficients, ascending), ascending, into off_r0 (off_r0, off_r1: D + 2 doubles each);
+// returns their number (0 when the polynomial is not of degree D in finite numbers)
+template <int D>
+GS_HD int gs_real_roots(const GsWs& w, int off_p, int off_r0, int off_r1, int bisect_low, int bisect_top, int newton) {
+    const double lead = w(off_p + D);
+    double big = 0.0;
+    for (int k = 0; k < D; ++k) {
+        const double v = gs_abs_or_inf(w(off_p + k));
+        big = v > big ? v : big;
+    }
+    if (!(fabs(lead) > 0.0)) return 0;
+    const double bound = 1.0 + big / fabs(lead);                   // Cauchy
+    if (!(bound < (double)INFINITY)) return 0;
+    int nprev = 0;
+    for (int m = 1; m <= D; ++m) {
+        const int s = D - m;                                       // q = the s-th derivative of p, degree m
+        double q[D + 1];
+        GS_UNROLL
+        for (int i = 0; i <= D; ++i) {
+            double c = 0.0;
+            if (i <= m) {
+                c = w(off_p + i + s);
+                for (int t = 1; t <= s; ++t) c = c * (double)(i + t);
+            }
+            q[i] = c;
+        }
+        const int iters = m == D ? bisect_top : bisect_low;
+        int nnew = 0;
+        double lo = -bound, flo = gs_horner<D>(q, lo);
+        for (int j = 0; j <= nprev; ++j) {
+            const double hi = j < nprev ? w(off_r0 + j) : bound;
+            const double fhi = gs_horner<D>(q, hi);
+            if ((flo > 0.0) != (fhi > 0.0)) {
+                double a = lo, b = hi;
+                for (int it = 0; it < iters; ++it) {
+                    const double mid = 0.5 * (a + b);
+                    const double fm = gs_horner<D>(q, mid);
+                    if ((fm > 0.0) == (flo > 0.0)) a = mid; else b = mid;
+                }
+                w(off_r1 + nnew) = 0.5 * (a + b);
+                ++nnew;
+            }
+            lo = hi; flo = fhi;
+        }
+        for (int j = 0; j < nnew; ++j) w(off_r0 + j) = w(off_r1 + j);
+        nprev = nnew;
+        if (m == D) {
+            double dq[D + 1];
+            GS_UNROLL
+            for (int i = 0; i < D; ++i) dq[i] = q[i + 1] * (double)(i + 1);
+            dq[D] = 0.0;
+            for (int j = 0; j < nnew; ++j) {
+                double z = w(off_r0 + j), f = gs_horner<D>(q, z);
+                for (int it = 0; it < newton; ++it) {
+                    const double zn = z - f / gs_horner<D>(dq, z);
+                    const double fn = gs_horner<D>(q, zn);
+                    if (fabs(fn) < fabs(f)) { z = zn; f = fn; }     // a NaN or a worse step is not taken
+                }
+                w(off_r0 + j) = z;
+            }
+        }
+    }
+    return nprev;
+}

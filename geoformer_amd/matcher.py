@@ -472,7 +472,7 @@ class ConsolidatedMatches(NamedTuple):
     matches: list            # per pair: [n_p, 2] int32 keypoint indices (into keypoints[pair_images[p, 0]], keypoints[pair_images[p, 1]])
 
 
-def consolidate_matches(pairs, results, sc_thres=0.25, qt_psize=48, qt_dthres=4, qt_unique=True, device='cuda'):
+def consolidate_matches(pairs, results, sc_thres=0.25, qt_psize=48, qt_dthres=4, qt_unique=True, device='cuda', keep=None):
     """[(path0, path1), ...] and the tuples match_many returned for them (either return convention: element 0 is the [n, 4] matches,
     element 3 the scores) -> ConsolidatedMatches: what COLMAP-style triangulation and localisation consume - one keypoint list per image
     and every match as two keypoint indices.  The reference's process_matches_and_keypoints_exporth5 with its defaults: matches scoring
@@ -481,16 +481,25 @@ def consolidate_matches(pairs, results, sc_thres=0.25, qt_psize=48, qt_dthres=4,
     a keypoint keeps only its best match per pair.  qt_psize <= 0 or qt_dthres <= 0: keypoints are merged only where coordinates are equal.
     Matches are taken as float32 (match_many's upscaled float64 is cast first; the reference stores float32 keypoints anyway).  One upload,
     ops.consolidate_keypoints on the device, bit-identical to the serial rule (csrc/keypoint_spec.h).  A pair without surviving rows gives
-    [0, 2]; a pair listed twice contributes twice, as in the reference."""
+    [0, 2]; a pair listed twice contributes twice, as in the reference.
+    keep: one boolean mask per pair (verify_matches(...).masks): only the rows it marks enter - the result is that of the same call on lists
+    with the other rows removed beforehand."""
     pairs = [tuple(p) for p in pairs]
     if len(pairs) != len(results):
         raise ValueError(f'consolidate_matches: {len(pairs)} pairs but {len(results)} results')
+    if keep is not None and len(keep) != len(pairs):
+        raise ValueError(f'consolidate_matches: {len(pairs)} pairs but {len(keep)} masks')
     index = {}
     pair_images = np.array([[index.setdefault(path, len(index)) for path in p] for p in pairs], np.int32).reshape(-1, 2)
     ms = [np.asarray(r[0], dtype=np.float32).reshape(-1, 4) for r in results]
     ss = [np.asarray(r[3], dtype=np.float32).reshape(-1) for r in results]
     if any(len(m) != len(s) for m, s in zip(ms, ss)):
         raise ValueError('consolidate_matches: a result whose matches and scores differ in length')
+    if keep is not None:
+        ks = [np.asarray(k, dtype=bool).reshape(-1) for k in keep]
+        if any(len(k) != len(m) for k, m in zip(ks, ms)):
+            raise ValueError('consolidate_matches: a mask whose length is not its pair\'s number of matches')
+        ms, ss = [m[k] for m, k in zip(ms, ks)], [x[k] for x, k in zip(ss, ks)]
     offsets = np.concatenate([[0], np.cumsum([len(m) for m in ms])]).astype(np.int32)
     M, P = int(offsets[-1]), len(pairs)
     # one upload: the four arrays as one block of 32-bit words
@@ -505,6 +514,49 @@ def consolidate_matches(pairs, results, sc_thres=0.25, qt_psize=48, qt_dthres=4,
         kp, kpo, ids, ido = kp.cpu().numpy(), kpo.cpu().numpy(), ids.cpu().numpy(), ido.cpu().numpy()
     return ConsolidatedMatches(list(index), [kp[kpo[i]:kpo[i + 1]].copy() for i in range(len(index))], pair_images,
                                [ids[ido[q]:ido[q + 1]].copy() for q in range(P)])
+
+
+# ---------------------------------------------------------------------------------------------
+# two-view geometric verification without intrinsics: a fundamental-matrix RANSAC per pair, all pairs in one call on the device
+# ---------------------------------------------------------------------------------------------
+class VerifiedMatches(NamedTuple):
+    F: np.ndarray            # [P, 3, 3] float64, x1^T F x0 = 0 in pixels, Frobenius norm 1 (zeros where RANSAC found no model)
+    n_inliers: np.ndarray    # [P] int32
+    verified: np.ndarray     # [P] bool: a model was found and it has at least min_inliers inliers
+    masks: list              # per pair: [n_p] bool, the inliers of a verified pair; all False otherwise
+
+
+def verify_matches(pairs, results, thr=1.0, min_inliers=15, sc_thres=0.25, iters=None, device='cuda'):
+    """Geometric verification of the matches of every pair, for image sets without poses or intrinsics: a detector-free matcher returns
+    confident-looking matches for pairs that show different scenes, and a track should only see matches that one epipolar geometry
+    explains.  Per pair a fundamental-matrix RANSAC (ops.ransac_fundamental: rows scoring below sc_thres or not finite take no part,
+    seven-point hypotheses, squared Sampson distance below thr^2 pixels; the rule is csrc/fund_solver.h) - one upload, three launches for
+    all pairs, one read back.  verified[p] = a model was found and n_inliers[p] >= min_inliers.  No refit and no planar-degeneracy test:
+    the F of a planar scene is valid but arbitrary, its inlier set is still the plane's.  pairs / results as consolidate_matches takes them."""
+    if len(pairs) != len(results):
+        raise ValueError(f'verify_matches: {len(pairs)} pairs but {len(results)} results')
+    P = len(results)
+    ms = [np.asarray(r[0], dtype=np.float32).reshape(-1, 4) for r in results]
+    ss = [np.asarray(r[3], dtype=np.float32).reshape(-1) for r in results]
+    if any(len(m) != len(x) for m, x in zip(ms, ss)):
+        raise ValueError('verify_matches: a result whose matches and scores differ in length')
+    if P == 0:
+        return VerifiedMatches(np.zeros((0, 3, 3)), np.zeros(0, np.int32), np.zeros(0, bool), [])
+    offsets = np.concatenate([[0], np.cumsum([len(m) for m in ms])]).astype(np.int32)
+    M = int(offsets[-1])
+    block = np.concatenate([a.reshape(-1).view(np.int32) for a in (*ms, *ss, offsets)])
+    with torch.cuda.device(device):
+        d = torch.from_numpy(block).to(device)
+        rs = ops.ransac_fundamental(d[:4 * M].view(torch.float32).view(M, 4), d[4 * M:5 * M].view(torch.float32), d[5 * M:], P, pixel_thr=thr,
+                                    sc_thres=sc_thres, iters=ops.FUND_RANSAC_ITERS if iters is None else iters)
+        out = torch.cat([rs[k].reshape(-1).view(torch.uint8) for k in ('F', 'valid', 'n_inliers', 'inliers')]).cpu().numpy()
+    F = out[:72 * P].view(np.float64).reshape(P, 3, 3).copy()
+    valid = out[72 * P:76 * P].view(np.int32)
+    nin = out[76 * P:80 * P].view(np.int32).copy()
+    inl = out[80 * P:].astype(bool)
+    verified = (valid == 1) & (nin >= min_inliers)
+    masks = [inl[offsets[p]:offsets[p + 1]].copy() if verified[p] else np.zeros(len(ms[p]), bool) for p in range(P)]
+    return VerifiedMatches(F, nin, verified, masks)
 
 
 def write_consolidated(out_dir, cm: ConsolidatedMatches):
@@ -572,6 +624,19 @@ def estimate_relative_pose(matches, K0, K1, thr=0.5, device='cuda'):
     if int(rs['valid'][0]) == 0:
         return None
     return rs['R'][0].cpu().numpy(), rs['t'][0].cpu().numpy(), rs['inliers'].cpu().numpy().astype(bool)
+
+
+def estimate_fundamental(matches, thr=1.0, device='cuda'):
+    """Fundamental-matrix RANSAC from [n,4] pixel matches on the device (no intrinsics needed; csrc/fund_solver.h); returns
+    (F with x1^T F x0 = 0 and Frobenius norm 1, inlier mask) or None."""
+    if len(matches) < 7:
+        return None
+    m = torch.as_tensor(np.asarray(matches), dtype=torch.float32, device=device)
+    offsets = torch.tensor([0, len(m)], dtype=torch.int32, device=device)
+    rs = ops.ransac_fundamental(m[:, :4].contiguous(), None, offsets, 1, pixel_thr=thr)
+    if int(rs['valid'][0]) == 0:
+        return None
+    return rs['F'][0].cpu().numpy(), rs['inliers'].cpu().numpy().astype(bool)
 
 
 def corner_error(H_pred, H_gt, w, h):
@@ -648,6 +713,7 @@ def eval_hpatches(matcher, data_root, ransac_thres=3, thres=(1, 3, 5, 10), scale
 #   python -m geoformer_amd.matcher hpatches /path/to/hpatches-sequences-release [--ckpt ...] [--preprocess device] [--reuse-features]
 #   python -m geoformer_amd.matcher pairs LIST | --all-pairs DIR  [--out DIR] [--batch B] [--cache-gb G] [--pad [--pad-waste R]]   (no reference counterpart)
 #                                         [--keypoints DIR [--sc-thres S] [--qt-psize P] [--qt-dthres D] [--no-qt-unique]]   (process_matches_and_keypoints_exporth5)
+#                                         [--verify [--verify-thr T] [--min-inliers K]]   (two-view verification: fundamental-matrix RANSAC per pair)
 # ---------------------------------------------------------------------------------------------
 def build_parser():
     """Defaults follow the reference per sub-command: `match` = inference.py:107 (imsize 640, matches scaled back to the
@@ -691,6 +757,11 @@ def build_parser():
     q.add_argument('--qt-dthres', type=float, default=4, help='with --keypoints: keypoints of a cell closer than this are merged')
     q.add_argument('--no-qt-unique', dest='qt_unique', action='store_false',
                    help='with --keypoints: keep every match of a merged keypoint instead of its best one per pair')
+    q.add_argument('--verify', action='store_true',
+                   help='verify every pair geometrically (fundamental-matrix RANSAC on the device, no intrinsics needed): each .npz of --out gains '
+                        'F, inliers and verified; with --keypoints only the inliers of verified pairs are consolidated and two_view.npz is written')
+    q.add_argument('--verify-thr', type=float, default=1.0, help='with --verify: inlier threshold, Sampson distance in pixels')
+    q.add_argument('--min-inliers', type=int, default=15, help='with --verify: a pair with fewer inliers is not verified')
     for p in (h, q):
         p.add_argument('--cache-gb', type=float, default=None,
                        help='byte budget of the feature store in GB: least recently used images are dropped and extracted again when '
@@ -728,15 +799,23 @@ def main(argv=None):
     if args.cmd == 'pairs':
         pairs = read_pair_list(args.list) if args.list is not None else all_pairs(args.all_pairs)
         results = matcher.match_many(pairs, batch=args.batch, pad=args.pad, max_waste=args.pad_waste)
+        vm = verify_matches(pairs, results, args.verify_thr, args.min_inliers, args.sc_thres, device=matcher.device) if args.verify else None
         if args.out:
             os.makedirs(args.out, exist_ok=True)
         for k, ((p0, p1), res) in enumerate(zip(pairs, results)):
             if args.out:
                 stem = '_'.join(os.path.splitext(os.path.basename(p))[0] for p in (p0, p1))
-                np.savez(os.path.join(args.out, f'{k:05d}_{stem}.npz'), matches=res[0], kpts1=res[1], kpts2=res[2], scores=res[3])
+                extra = {} if vm is None else {'F': vm.F[k], 'inliers': vm.masks[k], 'verified': vm.verified[k]}
+                np.savez(os.path.join(args.out, f'{k:05d}_{stem}.npz'), matches=res[0], kpts1=res[1], kpts2=res[2], scores=res[3], **extra)
+        if vm is not None:
+            print(f'{int(vm.verified.sum())} of {len(pairs)} pairs verified (thr {args.verify_thr} px, at least {args.min_inliers} inliers), '
+                  f'{sum(int(m.sum()) for m in vm.masks)} inlier matches')
         if args.keypoints:
-            cm = consolidate_matches(pairs, results, args.sc_thres, args.qt_psize, args.qt_dthres, args.qt_unique, device=matcher.device)
+            cm = consolidate_matches(pairs, results, args.sc_thres, args.qt_psize, args.qt_dthres, args.qt_unique, device=matcher.device,
+                                     keep=None if vm is None else vm.masks)
             write_consolidated(args.keypoints, cm)
+            if vm is not None:
+                np.savez(os.path.join(args.keypoints, 'two_view.npz'), pairs=cm.pair_images, F=vm.F, n_inliers=vm.n_inliers, verified=vm.verified)
             print(f'{len(cm.names)} images, {sum(len(k) for k in cm.keypoints)} keypoints, {sum(len(m) for m in cm.matches)} matches as keypoint '
                   f'indices -> {args.keypoints}')
         st = matcher.store

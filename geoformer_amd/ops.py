@@ -534,6 +534,35 @@ def ransac_essential(mkpts0, mkpts1, counts, N, K0, K1, pixel_thr=0.5, iters=POS
     return {'E': E, 'R': R, 't': t, 'valid': valid, 'n_inliers': nin, 'inliers': inl[:cap], 'hypothesis': best}
 
 
+FUND_RANSAC_ITERS = 512         # fixed, not adaptive; a positive multiple of 64.  An all-inlier sample of 7 at 50 % outliers: 98 % of the pairs
+
+
+def ransac_fundamental(matches, scores, offsets, N, pixel_thr=1.0, sc_thres=0.25, iters=FUND_RANSAC_ITERS, seed=RANSAC_SEED):
+    """Device fundamental-matrix RANSAC for the N pairs of a match list (csrc/fund_solver.h): two-view verification without intrinsics.
+    matches fp32 [M,4] pixel rows (x0, y0, x1, y1) sorted by pair, scores fp32 [M] or None, offsets int32 [N+1] on the device.  A row takes
+    part iff it is finite and (with scores) scores >= sc_thres.  Returns dict(F fp64 [N,3,3] of Frobenius norm 1 (x1^T F x0 = 0), valid
+    int32 [N], n_inliers int32 [N], inliers uint8 [M], hypothesis int32 [N,2])."""
+    _need_cuda(matches, offsets)
+    dev = matches.device
+    M = matches.shape[0]
+    m = _contig(matches.float().reshape(M, 4)) if M else torch.zeros(1, 4, dtype=torch.float32, device=dev)
+    sc = None if scores is None or M == 0 else _contig(scores.float())
+    off = _contig(offsets.to(device=dev, dtype=torch.int32))
+    if off.numel() != N + 1:
+        raise ValueError(f'ransac_fundamental: offsets has {off.numel()} entries for N = {N}')
+    F = torch.empty(N, 3, 3, dtype=torch.float64, device=dev)
+    valid = torch.empty(N, dtype=torch.int32, device=dev)
+    nin = torch.empty(N, dtype=torch.int32, device=dev)
+    best = torch.empty(N, 2, dtype=torch.int32, device=dev)
+    inl = torch.zeros(max(M, 1), dtype=torch.uint8, device=dev)
+    L_ = _lib.lib()
+    ws = _ws.get('fundamental', L_.gf_fundamental_workspace_bytes(N, M, max(int(iters), 1)), dev)
+    check(L_.gf_fundamental_ransac(_p(m), _p(sc), _p(off), N, M, float(sc_thres), float(pixel_thr), int(iters), int(seed), _p(F), _p(valid),
+                                   _p(nin), _p(best), _p(inl), _p(ws), ws.numel(), _stream()),
+          'gf_fundamental_ransac')
+    return {'F': F, 'valid': valid, 'n_inliers': nin, 'inliers': inl[:M], 'hypothesis': best}
+
+
 def epipolar_errors(mkpts0, mkpts1, m_bids, T_0to1, K0, K1):
     """Squared symmetric epipolar distance of every match under E = [t]x R of its pair's T_0to1 (metrics.py:30-69), fp32 [M]."""
     _need_cuda(mkpts0, mkpts1, m_bids, T_0to1)

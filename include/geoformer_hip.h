@@ -39,7 +39,7 @@ typedef enum { GF_F32 = 0, GF_F16 = 1, GF_BF16 = 2 } gf_dtype;
  * version 3 gives wrong channels) and GF_CONV_PAD16 now states that channels 196 .. 223 are padding; new: GF_CONV_S2, gf_lateral_upsample_add_nhwc. */
 /* Still 4 with gf_pos_encode_ptrs / gf_fine_gather_ptrs and gf_pos_encode_ragged / gf_fine_gather_ragged (with gf_map_record): entries appended at
  * the end change no existing one; a binding that needs them fails at load on the missing symbol (geoformer_amd/_lib.py binds every name).
- * Likewise with the gf_keypoint_* entries. */
+ * Likewise with the gf_keypoint_* entries and gf_fundamental_*. */
 #define GF_ABI_VERSION 4
 int gf_abi_version(void);
 const char* gf_last_error(void);
@@ -681,6 +681,28 @@ int gf_keypoint_filter(const float* scores, const int* pair_offsets, int P, int 
 int gf_keypoint_emit(const int* creator, const int* creator_scan, const int* pseg, const int* seg_adj, const float* cxy, const int* keep,
                      const int* keep_scan, const int* pair_offsets, const int* pair_images, int P, int M, const int* owner,
                      const int* kp_offsets, float* keypoints, int* ids, int* pair_offsets_out, int* counts, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Two-view geometric verification without intrinsics: fundamental-matrix RANSAC for every pair of a match list
+ * (the uncalibrated counterpart of the per-pair geometric verification in eval_tool/immatch/utils/localize_sfm_helper.py; the reference has no
+ * fundamental-matrix code).  OpenCV parity is unpinned; the algorithm is the one stated in geoformer_amd/csrc/fund_solver.h (box conditioning,
+ * seven-point minimal solver, Sampson inliers in pixels; no refit, no local optimisation, no planar-degeneracy test), which also compiles for
+ * the host (csrc/host/fund_host.cpp): bit-exact against that build.
+ *   gf_fundamental_ransac
+ *     matches fp32 [M,4] (x0, y0, x1, y1 in pixels), scores fp32 [M] or NULL, offsets int32 [N + 1] in DEVICE memory (ascending, first 0, last M:
+ *     the rows of pair n - the layout of the keypoint consolidation; entries are clamped into [0, M] before use).  A row takes part iff its four
+ *     coordinates are finite and, with scores, its score is not NaN and >= sc_thres (the filter of gf_keypoint_keys).
+ *     iters: FIXED number of hypotheses per pair, a positive multiple of 64; hypothesis t of pair n draws its rows from (seed, n, t).
+ *     N > 0 and N * (iters / 64) <= 16777216 (the workgroups of one launch); anything else is GF_ERR_INVALID_ARGUMENT, never wrapped.
+ *     outputs: F fp64 [N,9] (x1^T F x0 = 0 in pixels, Frobenius norm 1; zeros when not valid), valid int32 [N] (1 iff at least 7 rows take part,
+ *     both bounding boxes have an extent and a hypothesis produced a solution), n_inliers int32 [N], best int32 [N,2] (hypothesis, root; -1),
+ *     inliers uint8 [M] (the winner's inlier set over the original rows: squared Sampson distance < pixel_thr^2; filtered rows 0).
+ *     workspace: gf_fundamental_workspace_bytes(N, M, iters) bytes.  Three launches, no host synchronisation, bit-identical from run to run.
+ * ------------------------------------------------------------------------------------------ */
+size_t gf_fundamental_workspace_bytes(int N, int M, int iters);
+int gf_fundamental_ransac(const float* matches, const float* scores, const int32_t* offsets, int N, int M, float sc_thres,
+                          float pixel_thr, int iters, uint32_t seed, double* F, int32_t* valid, int32_t* n_inliers, int32_t* best,
+                          uint8_t* inliers, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
