@@ -8,7 +8,7 @@
 //   fs_box_norm     Conditioning.  Per pair and image the bounding box of the surviving points: centre -> 0, half the longer side -> 1.
 //                   Min and max do not depend on the order of reduction, so the parallel form gives the serial form's bits (a mean / RMS
 //                   normalisation would not).  A zero extent makes the pair invalid.
-//   fs_draw7        seven distinct surviving rows of hypothesis t of pair n from (seed, n, t) and an attempt counter, as ps_draw5; a candidate
+//   fs_draw7        seven distinct surviving rows of hypothesis t of pair n from (seed, n, t) and an attempt counter, as gs_draw_distinct; a candidate
 //                   equal to an earlier one in EITHER image's point is drawn again.
 //   fs_seven_point  7x9 system x1^T F x0 = 0 in normalised coordinates -> its 2-dimensional null space (F1, F2) by Gauss-Jordan with full
 //                   pivoting -> the cubic det(x F1 + F2) in closed form (determinants and mixed cofactor sums).  The pencil is read from the
@@ -18,7 +18,7 @@
 //                   (fixed bisection counts + guarded Newton): one or three.  Each solution is scaled to Frobenius norm 1, taken back to
 //                   pixels as T1^T F T0 and scaled to norm 1 again.  Non-finite input, a rank-deficient system or seven coincident points
 //                   give 0 solutions.
-//   fs_sampson      the squared Sampson distance in pixels; inlier iff < thr^2 (a NaN is never an inlier).
+//   fs_inlier       the squared Sampson distance in pixels (gs_sampson); inlier iff < thr^2 (a NaN is never an inlier).
 //   selection       most inliers, then the smallest hypothesis, then the smallest root.  valid = 1 iff at least FS_MIN_MATCHES rows survive,
 //                   both boxes have an extent and some hypothesis produced a solution.  The mask is the winner's inlier set over the pair's
 //                   ORIGINAL rows; filtered rows are 0.
@@ -36,9 +36,8 @@
 #endif
 
 #define FS_MAX_ROOTS 3
-#define FS_HYP_PER_WG 64          /* hypotheses one workgroup of fund_score solves: iters must be a positive multiple */
+#define FS_HYP_PER_WG 64          /* hypotheses one workgroup of rt_score<FundModel> solves: iters must be a positive multiple */
 #define FS_MIN_MATCHES 7
-#define FS_DRAW_ATTEMPTS 16
 #define FS_BISECT_LOW 40
 #define FS_BISECT_TOP 56
 #define FS_NEWTON 4
@@ -78,7 +77,7 @@ GS_HD int fs_draw7(uint32_t seed, uint32_t sample, uint32_t t, int cnt, const fl
     GS_UNROLL
     for (int k = 0; k < 7; ++k) {
         int found = 0;
-        for (uint32_t attempt = 0; attempt < FS_DRAW_ATTEMPTS && !found && ok; ++attempt) {
+        for (uint32_t attempt = 0; attempt < GS_DRAW_ATTEMPTS && !found && ok; ++attempt) {
             const int c = (int)(draw(seed, sample, t, (uint32_t)k, attempt) % (uint32_t)cnt);
             const float* q = m + 4 * (long)rows[c];
             const float q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
@@ -190,13 +189,7 @@ GS_HD int fs_seven_point(const double (&x0)[7][2], const double (&x1)[7][2], con
     return n;
 }
 
-// squared Sampson distance of a pixel match under F
-GS_HD double fs_sampson(const double (&F)[9], double x0, double y0, double x1, double y1) {
-    const double a0 = (F[0] * x0 + F[1] * y0) + F[2], a1 = (F[3] * x0 + F[4] * y0) + F[5], a2 = (F[6] * x0 + F[7] * y0) + F[8];
-    const double b0 = (F[0] * x1 + F[3] * y1) + F[6], b1 = (F[1] * x1 + F[4] * y1) + F[7];
-    const double num = (x1 * a0 + y1 * a1) + a2;
-    return (num * num) / (((a0 * a0 + a1 * a1) + b0 * b0) + b1 * b1);
-}
+// inlier iff the squared Sampson distance of the pixel match under F is below thr^2
 GS_HD int fs_inlier(const double (&F)[9], const float* m4, double thr2) {
-    return fs_sampson(F, (double)m4[0], (double)m4[1], (double)m4[2], (double)m4[3]) < thr2;      // a NaN is never an inlier
+    return gs_sampson(F, (double)m4[0], (double)m4[1], (double)m4[2], (double)m4[3]) < thr2;      // a NaN is never an inlier
 }

@@ -39,7 +39,7 @@ int gf_pose_host_ransac(const float* mk0, const float* mk1, int n, const float* 
     double best[9];
     for (int t = 0; t < iters; ++t) {
         int idx[5];
-        if (!ps_draw5(seed, sample, (uint32_t)t, n, idx)) continue;
+        if (!gs_draw_distinct<5>(seed, sample, (uint32_t)t, n, idx)) continue;
         double x0[5][2], x1[5][2];
         for (int k = 0; k < 5; ++k) {
             ps_normalise(K0, mk0[2 * idx[k]], mk0[2 * idx[k] + 1], x0[k][0], x0[k][1]);

@@ -8,15 +8,11 @@
 //   fund_prepare : grid N, 256 threads.  Stable compaction of the pair's surviving rows (fs_row_valid) into the workspace, 256 rows at a
 //                  time: ballot per wave, prefix = popcount of the lower lanes + the counts of the lower waves, in row order.  Min / max
 //                  of the surviving points per image through an LDS tree (order-free: min and max are exact), then fs_box_norm.
-//   fund_score   : grid N * (iters / 64), 256 threads; block b works for pair b / (iters / 64).  The 64 lanes of wave 0 each draw the 7
-//                  rows of one hypothesis and run the seven-point solver with EVERYTHING it indexes at run time - the 7x9 system, the
-//                  null space, the cubic, its roots, the up to 3 solutions - in an LDS tile of FS_WS_DOUBLES doubles per hypothesis,
-//                  interleaved across the 64 solver lanes (element i of hypothesis h at ws[64 i + h]: lanes hit 64 consecutive doubles,
-//                  conflict-free).  Nothing of the elimination lives in a lane's scratch memory (k_ransac.hip's header records what that
-//                  cost the homography kernel).  Then all four waves score: wave w owns hypotheses 16 w .. 16 w + 15, walks the pair's
-//                  surviving rows 64 at a time and counts the Sampson inliers of every root with one ballot + popcount - a wave-uniform
-//                  integer, no shuffle reduction, no float atomics.  The block's best (most inliers, smallest hypothesis, smallest root)
-//                  goes to the workspace with its F: 11 words per block, not per hypothesis.
+//   rt_score<FundModel> : grid N * (iters / 64), 256 threads: the scoring kernel of ransac_tile.h.  The 64 lanes of wave 0 each draw the
+//                  7 rows of one hypothesis and run the seven-point solver - the 7x9 system, the null space, the cubic, its roots, the up
+//                  to 3 solutions - in the LDS tile; the four waves count the Sampson inliers of every root over the pair's surviving
+//                  rows.  The block's best (most inliers, smallest hypothesis, smallest root) goes to the workspace with its F: 11 words
+//                  per block, not per hypothesis.
 //                  FS_HYP_PER_WG = 64: the tile is 64 x 81 x 8 B = 41,472 B; 128 hypotheses (82,944 B) would pass the 64 KiB a kernel may
 //                  declare statically - the static LDS limit bound the choice - and 64 is also exactly one wave of solver lanes.
 //   fund_final   : grid N, 256 threads.  Best block (same order), then the winner's inlier set over the pair's ORIGINAL rows (filtered
@@ -24,27 +20,24 @@
 // No host synchronisation; every output is the same in every run.
 #include "gf_common.h"
 #include "fund_solver.h"
+#include "ransac_tile.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int FUND_MAX_BLOCKS = 1 << 24;      // grid x 256 threads must stay below 2^32 threads
-
 struct FundArgs {
     const float* m;          // [M][4] x0, y0, x1, y1 (px), sorted by pair
     const float* scores;     // [M] or null
     const int32_t* offsets;  // [N + 1]
-    int N, M, iters, nblk;
+    int N, M;
     float sc_thres;
     double thr2;
     uint32_t seed;
     int32_t* rows;           // [M]        per pair: the surviving rows (relative to the pair's first), ascending
     int32_t* use;            // [N]        surviving rows where the pair can be estimated (>= 7, both boxes with an extent), else 0
     double* norm;            // [N][6]
-    double* blk_F;           // [N][nblk][9]  best solution of every block
-    long long* blk_key;      // [N][nblk]     its inlier count * 2^32 + (2^31 - 1 - hypothesis); -1: no solution
-    int32_t* blk_root;       // [N][nblk]
+    RtBlocks blk;            // every block's best F
     double* F;               // [N][9]
     int32_t* valid;          // [N]
     int32_t* n_inliers;      // [N]
@@ -126,87 +119,49 @@ __global__ __launch_bounds__(256) void fund_prepare(FundArgs a) {
     }
 }
 
-__global__ __launch_bounds__(256) void fund_score(FundArgs a) {
-    __shared__ double ws[FS_WS_DOUBLES * FS_HYP_PER_WG];
-    __shared__ int s_nroot[FS_HYP_PER_WG];
-    __shared__ int s_cnt[FS_HYP_PER_WG * FS_MAX_ROOTS];
-    __shared__ long long s_key[FS_HYP_PER_WG];
-    __shared__ int s_root[FS_HYP_PER_WG];
-    const int n = (int)(blockIdx.x / (unsigned)a.nblk), hb = (int)(blockIdx.x % (unsigned)a.nblk);
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int cnt = a.use[n];
-    if (cnt == 0) return;                                              // (uniform per block; fund_final does not read blk_* then)
-    int off, len;
-    fund_range(a, n, off, len);
-    const float* m = a.m + 4 * (size_t)off;
-    const int32_t* rows = a.rows + off;
-    for (int i = tid; i < FS_HYP_PER_WG * FS_MAX_ROOTS; i += 256) s_cnt[i] = 0;
-    if (tid < FS_HYP_PER_WG) {
-        const int t = hb * FS_HYP_PER_WG + tid;                        // < iters: iters is a multiple of FS_HYP_PER_WG
-        int idx[7], nr = 0;
-        if (fs_draw7(a.seed, (uint32_t)n, (uint32_t)t, cnt, m, rows, idx)) {
-            double x0[7][2], x1[7][2], nm[6];
-#pragma unroll
-            for (int k = 0; k < 6; ++k) nm[k] = a.norm[6 * (size_t)n + k];
-#pragma unroll
-            for (int k = 0; k < 7; ++k) {
-                const float* q = m + 4 * (size_t)rows[idx[k]];
-                x0[k][0] = (double)q[0]; x0[k][1] = (double)q[1]; x1[k][0] = (double)q[2]; x1[k][1] = (double)q[3];
-            }
-            nr = fs_seven_point(x0, x1, nm, GsWs{ws + tid, FS_HYP_PER_WG});
-        }
-        s_nroot[tid] = nr;
+// the fundamental-matrix model of rt_score: rows are reached through the compacted list, samples are conditioned by the pair's boxes
+struct FundModel {
+    static constexpr int HYP = FS_HYP_PER_WG, ROOTS = FS_MAX_ROOTS, WS = FS_WS_DOUBLES, OFF_SOL = FS_OFF_F;
+    typedef FundArgs Args;
+    struct Row { float q[4]; };
+    const float* m;          // the pair's matches
+    const int32_t* rows;     // its surviving rows
+    const double* norm;      // [6]
+    uint32_t seed, n;
+    int cnt;
+    double thr2;
+    __device__ __forceinline__ int init(const FundArgs& a, int pair) {
+        int off, len;
+        fund_range(a, pair, off, len);
+        m = a.m + 4 * (size_t)off; rows = a.rows + off; norm = a.norm + 6 * (size_t)pair;
+        seed = a.seed; n = (uint32_t)pair; thr2 = a.thr2;
+        return cnt = a.use[pair];
     }
-    __syncthreads();
-    // ---- scoring: this wave's 16 hypotheses against every surviving row of the pair
-    for (int i0 = 0; i0 < cnt; i0 += 64) {
-        const int i = i0 + lane;
-        const bool have = i < cnt;
-        float q[4] = {0.f, 0.f, 0.f, 0.f};
+    __device__ __forceinline__ Row load(int i, bool have) const {
+        Row r = {{0.f, 0.f, 0.f, 0.f}};
         if (have) {
             const float* p = m + 4 * (size_t)rows[i];
-            q[0] = p[0]; q[1] = p[1]; q[2] = p[2]; q[3] = p[3];
+            r.q[0] = p[0]; r.q[1] = p[1]; r.q[2] = p[2]; r.q[3] = p[3];
         }
-        for (int g = 0; g < FS_HYP_PER_WG / 4; ++g) {
-            const int h = wave * (FS_HYP_PER_WG / 4) + g, nr = s_nroot[h];
-            for (int r = 0; r < nr; ++r) {
-                double F[9];
+        return r;
+    }
+    __device__ __forceinline__ int solve(int t, const GsWs& w) const {
+        int idx[7];
+        if (!fs_draw7(seed, n, (uint32_t)t, cnt, m, rows, idx)) return 0;
+        double x0[7][2], x1[7][2], nm[6];
 #pragma unroll
-                for (int k = 0; k < 9; ++k) F[k] = ws[(FS_OFF_F + 9 * r + k) * FS_HYP_PER_WG + h];
-                const int in = have && fs_inlier(F, q, a.thr2);
-                const int pc = __popcll(__ballot(in));
-                if (lane == 0) s_cnt[h * FS_MAX_ROOTS + r] += pc;     // this wave alone touches its hypotheses' counters
-            }
+        for (int k = 0; k < 6; ++k) nm[k] = norm[k];
+#pragma unroll
+        for (int k = 0; k < 7; ++k) {
+            const Row r = load(idx[k], true);
+            x0[k][0] = (double)r.q[0]; x0[k][1] = (double)r.q[1]; x1[k][0] = (double)r.q[2]; x1[k][1] = (double)r.q[3];
         }
+        return fs_seven_point(x0, x1, nm, w);
     }
-    __syncthreads();
-    if (tid < FS_HYP_PER_WG) {
-        const int t = hb * FS_HYP_PER_WG + tid, nr = s_nroot[tid];
-        int bc = -1, br = -1;
-        for (int r = 0; r < nr; ++r) {
-            const int c = s_cnt[tid * FS_MAX_ROOTS + r];
-            if (c > bc) { bc = c; br = r; }
-        }
-        s_key[tid] = bc < 0 ? -1ll : (((long long)bc << 32) | (long long)(0x7FFFFFFF - t));
-        s_root[tid] = br;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        long long key = -1;
-        int bh = -1;
-        for (int h = 0; h < FS_HYP_PER_WG; ++h)
-            if (s_key[h] > key) { key = s_key[h]; bh = h; }
-        const size_t o = (size_t)n * a.nblk + hb;
-        a.blk_key[o] = key;
-        a.blk_root[o] = bh < 0 ? -1 : s_root[bh];
-        if (bh >= 0)
-            for (int k = 0; k < 9; ++k) a.blk_F[o * 9 + k] = ws[(FS_OFF_F + 9 * s_root[bh] + k) * FS_HYP_PER_WG + bh];
-    }
-}
+    __device__ __forceinline__ int inlier(const double (&F)[9], const Row& r) const { return fs_inlier(F, r.q, thr2); }
+};
 
 __global__ __launch_bounds__(256) void fund_final(FundArgs a) {
-    __shared__ long long sh_key[256];
-    __shared__ int sh_blk[256];
     __shared__ double sh_F[9];
     __shared__ int sh_nin;
     const int n = blockIdx.x, t = threadIdx.x, lane = t & 63;
@@ -215,24 +170,10 @@ __global__ __launch_bounds__(256) void fund_final(FundArgs a) {
     uint8_t* mask = a.inliers + off;
     const float* m = a.m + 4 * (size_t)off;
     const float* sc = a.scores ? a.scores + off : nullptr;
-    // ---- best block: max count, ties -> smallest hypothesis (the key's low word)
-    long long key = -1;
-    int blk = -1;
-    if (a.use[n] > 0)
-        for (int i = t; i < a.nblk; i += 256) {
-            const long long kk = a.blk_key[(size_t)n * a.nblk + i];
-            if (kk > key) { key = kk; blk = i; }
-        }
-    sh_key[t] = key;
-    sh_blk[t] = blk;
     if (t == 0) sh_nin = 0;
-    __syncthreads();
-    for (int s = 128; s >= 1; s >>= 1) {
-        if (t < s && sh_key[t + s] > sh_key[t]) { sh_key[t] = sh_key[t + s]; sh_blk[t] = sh_blk[t + s]; }      // keys are distinct unless -1
-        __syncthreads();
-    }
-    key = sh_key[0];
-    blk = sh_blk[0];
+    // ---- best block: most inliers, then the smallest hypothesis
+    size_t o;
+    const long long key = rt_best_block(a.blk, n, a.use[n] > 0, o);
     if (key < 0) {                                                     // (uniform: every thread holds the same key)
         for (int i = t; i < len; i += 256) mask[i] = 0;
         if (t == 0) {
@@ -241,8 +182,7 @@ __global__ __launch_bounds__(256) void fund_final(FundArgs a) {
         }
         return;
     }
-    const size_t o = (size_t)n * a.nblk + blk;
-    if (t < 9) sh_F[t] = a.blk_F[o * 9 + t];
+    if (t < 9) sh_F[t] = a.blk.sol[o * 9 + t];
     __syncthreads();
     double F[9];
 #pragma unroll
@@ -258,7 +198,7 @@ __global__ __launch_bounds__(256) void fund_final(FundArgs a) {
     if (t == 0) {
         for (int k = 0; k < 9; ++k) a.F[9 * (size_t)n + k] = F[k];
         a.valid[n] = 1; a.n_inliers[n] = sh_nin;
-        a.best[2 * n] = 0x7FFFFFFF - (int)(key & 0xFFFFFFFFll); a.best[2 * n + 1] = a.blk_root[o];
+        a.best[2 * n] = rt_key_hyp(key); a.best[2 * n + 1] = a.blk.root[o];
     }
 }
 
@@ -268,8 +208,7 @@ extern "C" size_t gf_fundamental_workspace_bytes(int N, int M, int iters) {
     if (N <= 0 || M < 0 || iters <= 0) return 0;
     const size_t nb = (size_t)N * ((size_t)(iters + FS_HYP_PER_WG - 1) / FS_HYP_PER_WG);
     return gf_align_up((size_t)M * sizeof(int32_t), 256) + gf_align_up((size_t)N * sizeof(int32_t), 256) +
-           gf_align_up((size_t)N * 6 * sizeof(double), 256) + gf_align_up(nb * 9 * sizeof(double), 256) +
-           gf_align_up(nb * sizeof(long long), 256) + gf_align_up(nb * sizeof(int32_t), 256);
+           gf_align_up((size_t)N * 6 * sizeof(double), 256) + rt_blocks_bytes(nb);
 }
 
 extern "C" int gf_fundamental_ransac(const float* matches, const float* scores, const int32_t* offsets, int N, int M, float sc_thres,
@@ -278,7 +217,7 @@ extern "C" int gf_fundamental_ransac(const float* matches, const float* scores, 
     GF_CHECK_ARG(matches && offsets && F && valid && n_inliers && best && inliers, "null pointer");
     GF_CHECK_ARG(M >= 0, "need M >= 0");
     GF_CHECK_ARG(iters > 0 && iters % FS_HYP_PER_WG == 0, "iters must be a positive multiple of 64 (the hypotheses of one workgroup)");
-    GF_CHECK_ARG(N > 0 && (long long)N * (iters / FS_HYP_PER_WG) <= FUND_MAX_BLOCKS,
+    GF_CHECK_ARG(N > 0 && (long long)N * (iters / FS_HYP_PER_WG) <= RT_MAX_BLOCKS,
                  "N out of range: need N > 0 and N * (iters / 64) <= 16777216 workgroups in one launch");
     GF_CHECK_ARG(pixel_thr > 0.f && pixel_thr < INFINITY, "pixel_thr must be positive and finite");
     if (workspace == nullptr || workspace_bytes < gf_fundamental_workspace_bytes(N, M, iters)) {
@@ -286,21 +225,18 @@ extern "C" int gf_fundamental_ransac(const float* matches, const float* scores, 
         return GF_ERR_WORKSPACE;
     }
     FundArgs a;
-    a.m = matches; a.scores = scores; a.offsets = offsets; a.N = N; a.M = M; a.iters = iters; a.nblk = iters / FS_HYP_PER_WG;
+    a.m = matches; a.scores = scores; a.offsets = offsets; a.N = N; a.M = M;
     a.sc_thres = sc_thres; a.thr2 = (double)pixel_thr * (double)pixel_thr; a.seed = seed;
-    const size_t nb = (size_t)N * a.nblk;
     GfCarver cv(workspace);
     a.rows = cv.take<int32_t>((size_t)M);
     a.use = cv.take<int32_t>((size_t)N);
     a.norm = cv.take<double>((size_t)N * 6);
-    a.blk_F = cv.take<double>(nb * 9);
-    a.blk_key = cv.take<long long>(nb);
-    a.blk_root = cv.take<int32_t>(nb);
+    a.blk = rt_blocks_take(cv, N, iters / FS_HYP_PER_WG);
     a.F = F; a.valid = valid; a.n_inliers = n_inliers; a.best = best; a.inliers = inliers;
     hipStream_t st = (hipStream_t)stream;
     void* tok = gf_prof_begin("fund_ransac", st, (double)N * iters);
     fund_prepare<<<N, 256, 0, st>>>(a);
-    fund_score<<<(unsigned)nb, 256, 0, st>>>(a);
+    rt_score<FundModel><<<(unsigned)N * a.blk.nblk, 256, 0, st>>>(a);
     fund_final<<<N, 256, 0, st>>>(a);
     gf_prof_end("fund_ransac", tok, st);
     GF_CHECK_LAUNCH();

@@ -16,9 +16,12 @@
 //   pose_final : grid N.  Best hypothesis (most inliers, then smallest index), inlier mask, E -> (R1, R2, +-t), cheirality vote over
 //                the inliers (integer counts through LDS atomics: order-free), outputs.
 //   epipolar_errors : one thread per match, fp64 arithmetic, one rounding to fp32.
-// No host synchronisation: match counts are read from device memory.
+// No host synchronisation: match counts are read from device memory (rt_counts_range).  pose_score is the scoring stage that ransac_tile.h
+// states as rt_score<Model>, kept hand-written with per-hypothesis results: on rt_score's per-block winners it measured 1 - 3.5 % slower
+// (profiles/ransac_tile.txt).
 #include "gf_common.h"
 #include "pose_solver.h"
+#include "ransac_tile.h"
 
 #pragma clang fp contract(off)
 
@@ -45,22 +48,13 @@ struct PoseArgs {
     uint8_t* inliers;        // [cap]
 };
 
-// the pair's slice of the match list, clamped to the buffers' capacity (counts come from device memory)
-__device__ __forceinline__ void pose_range(const PoseArgs& a, int n, int& off, int& cnt) {
-    off = 0;
-    for (int b = 0; b < n; ++b) off += max(a.counts[1 + b], 0);
-    cnt = max(a.counts[1 + n], 0);
-    if (off > a.capacity) off = a.capacity;
-    if (cnt > a.capacity - off) cnt = a.capacity - off;
-}
-
 __global__ __launch_bounds__(256) void pose_score(PoseArgs a) {
     __shared__ double ws[PS_WS_DOUBLES * PS_HYP_PER_WG];
     __shared__ int s_nroot[PS_HYP_PER_WG];
     __shared__ int s_cnt[PS_HYP_PER_WG * PS_MAX_ROOTS];
     const int n = blockIdx.y, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     int off, cnt;
-    pose_range(a, n, off, cnt);
+    rt_counts_range(a.counts, n, a.capacity, off, cnt);
     if (cnt < PS_MIN_MATCHES) return;                                  // (uniform per block; pose_final does not read hyp_* then)
     const float* k0 = a.mk0 + 2 * (size_t)off;
     const float* k1 = a.mk1 + 2 * (size_t)off;
@@ -71,7 +65,7 @@ __global__ __launch_bounds__(256) void pose_score(PoseArgs a) {
     if (tid < PS_HYP_PER_WG) {
         const int t = blockIdx.x * PS_HYP_PER_WG + tid;                // < iters: iters is a multiple of PS_HYP_PER_WG
         int idx[5], nr = 0;
-        if (ps_draw5(a.seed, (uint32_t)n, (uint32_t)t, cnt, idx)) {
+        if (gs_draw_distinct<5>(a.seed, (uint32_t)n, (uint32_t)t, cnt, idx)) {
             double x0[5][2], x1[5][2];
 #pragma unroll
             for (int k = 0; k < 5; ++k) {
@@ -126,19 +120,19 @@ __global__ __launch_bounds__(256) void pose_final(PoseArgs a) {
     __shared__ int sh_votes[4], sh_nin;
     const int n = blockIdx.x, t = threadIdx.x;
     int off, cnt;
-    pose_range(a, n, off, cnt);
+    rt_counts_range(a.counts, n, a.capacity, off, cnt);
     uint8_t* mask = a.inliers + off;
     const float* k0 = a.mk0 + 2 * (size_t)off;
     const float* k1 = a.mk1 + 2 * (size_t)off;
     const float* K0 = a.K0 + 9 * n;
     const float* K1 = a.K1 + 9 * n;
-    // ---- best hypothesis: max count, ties -> smallest index  (key = count * 2^32 + (2^31 - 1 - index))
+    // ---- best hypothesis: most inliers, then the smallest index (rt_key)
     long long key = -1;
     if (cnt >= PS_MIN_MATCHES)
         for (int i = t; i < a.iters; i += 256) {
             const int c = a.hyp_cnt[(size_t)n * a.iters + i];
             if (c >= 0) {
-                const long long kk = ((long long)c << 32) | (long long)(0x7FFFFFFF - i);
+                const long long kk = rt_key(c, i);
                 key = kk > key ? kk : key;
             }
         }
@@ -151,8 +145,7 @@ __global__ __launch_bounds__(256) void pose_final(PoseArgs a) {
         __syncthreads();
     }
     key = sh_key[0];
-    const int best_cnt = key < 0 ? -1 : (int)(key >> 32);
-    const int best_t = key < 0 ? -1 : 0x7FFFFFFF - (int)(key & 0xFFFFFFFFll);
+    const int best_cnt = rt_key_count(key), best_t = rt_key_hyp(key);
     bool have = best_cnt >= PS_MIN_MATCHES;                            // (uniform: every thread holds the same key)
     double E[9], R1[9], R2[9], tt[3];
     int dec = 0;

@@ -9,14 +9,16 @@
 //                  count the inliers of the wave's 8 hypotheses in one pass over the matches.
 //                  [Round 3: one hypothesis per wave, lane 0 solving alone on a scratch-memory matrix - the serial
 //                  solve, not the scoring, was the kernel's 144 us.]
-//   ransac_final : grid N: best hypothesis (most inliers, then smallest t), inlier mask, Hartley-
+//   ransac_final : grid N: best hypothesis (most inliers, then smallest t: rt_key), inlier mask, Hartley-
 //                  normalised least-squares refit (block reductions; the 8x8 solves on eight lanes as above),
 //                  Levenberg-Marquardt steps, M, M^-1 (fp64 adjugate), fp32 casts.
-// No host synchronisation: match counts are read from device memory.
+// No host synchronisation: match counts are read from device memory (rt_counts_range: clamped to the buffers' capacity).  What the three
+// RANSAC files share - the slice helper, the selection key and its block reduction, the hypothesis-tile scoring stage of the two solvers
+// that need an LDS workspace - is described once in ransac_tile.h; the draw is gs_draw_distinct of solver_common.h.
 #include <math.h>
 
 #include "gf_common.h"
-#include "gf_hash.h"                      // mix32 / draw: shared with k_pose.hip
+#include "ransac_tile.h"
 
 #pragma clang fp contract(off)
 
@@ -26,7 +28,7 @@ struct RsArgs {
     const float* mk0;        // [cap][2] matched keypoints (px) of image0, sorted by sample
     const float* mk1;
     const int32_t* counts;   // [1+N]: total, per sample
-    int N, iters;
+    int N, iters, capacity;
     float scale;             // hw0_i[0] // hw0_c[0]
     const float* scale0;     // [N][2] or null
     const float* scale1;
@@ -46,40 +48,9 @@ struct RsArgs {
     uint8_t* keep;           // [cap] 1 = match feeds the inlier maps (inlier, or any match when no model)
 };
 
-__device__ int rs_solve(double* a, double* b, int n) {
-    for (int c = 0; c < n; ++c) {
-        int p = c;
-        double best = fabs(a[c * n + c]);
-        if (!(best == best)) best = INFINITY;              /* a non-finite entry in the column fails the solve (round 5: NaN keypoints) */
-        for (int r = c + 1; r < n; ++r) {
-            double v = fabs(a[r * n + c]);
-            if (!(v == v)) v = INFINITY;
-            if (v > best) { best = v; p = r; }
-        }
-        if (!(best > 1e-12) || best == INFINITY) return 0;
-        if (p != c) {
-            for (int k = 0; k < n; ++k) { const double tmp = a[c * n + k]; a[c * n + k] = a[p * n + k]; a[p * n + k] = tmp; }
-            const double tb = b[c]; b[c] = b[p]; b[p] = tb;
-        }
-        const double inv = 1.0 / a[c * n + c];
-        for (int r = c + 1; r < n; ++r) {
-            const double f = a[r * n + c] * inv;
-            if (f != 0.0) {
-                for (int k = c; k < n; ++k) a[r * n + k] = a[r * n + k] - f * a[c * n + k];
-                b[r] = b[r] - f * b[c];
-            }
-        }
-    }
-    for (int c = n - 1; c >= 0; --c) {
-        double s = b[c];
-        for (int k = c + 1; k < n; ++k) s = s - a[c * n + k] * b[k];
-        b[c] = s / a[c * n + c];
-    }
-    return 1;
-}
-
-// rs_solve with the 8 rows of the system on 8 consecutive lanes (lane r of the group holds row r: a[0..7] and b in registers):
-// the same partial-pivot elimination, element operation for element operation - a row operation a[r][k] - f a[c][k] is the same
+// The serial 8x8 solve of oracle/ransac_oracle.c (solve) with the 8 rows of the system on 8 consecutive lanes (lane r of the group holds
+// row r: a[0..7] and b in registers): the same partial-pivot elimination, element operation for element operation - a row operation
+// a[r][k] - f a[c][k] is the same
 // IEEE operation on whichever lane it runs, the pivot is the FIRST row of maximal |a[r][c]| as in the serial loop, and the back
 // substitution subtracts a[c][k] x[k] in ascending k - so the solution has the serial code's bits (the inlier mask test against
 // oracle/ransac_oracle.c requires it).  Every lane of the group returns the solution x[0..7] and the ok flag.  The caller's
@@ -151,18 +122,12 @@ __device__ __forceinline__ int rs_inlier(const double* h, double x, double y, do
     return dx * dx + dy * dy <= thr2;
 }
 
-__device__ __forceinline__ void rs_range(const RsArgs& a, int n, int& off, int& cnt) {
-    off = 0;
-    for (int b = 0; b < n; ++b) off += a.counts[1 + b];
-    cnt = a.counts[1 + n];
-}
-
 // integer keypoints exactly as the reference derives them: .long() of the float px coordinates,
 // then (only with per-image scales) kp / (scale*scale0[b]) * scale and .long() again
 __global__ void ransac_keypoints(RsArgs a) {
     const int n = blockIdx.y;
     int off, cnt;
-    rs_range(a, n, off, cnt);
+    rt_counts_range(a.counts, n, a.capacity, off, cnt);
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += gridDim.x * blockDim.x) {
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
@@ -186,24 +151,14 @@ __global__ __launch_bounds__(256) void ransac_score(RsArgs a) {
     const int n = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63, grp = lane >> 3, r = lane & 7;
     const int t = (blockIdx.x * 4 + wave) * 8 + grp;                   // this lane group's hypothesis
     int off, cnt;
-    rs_range(a, n, off, cnt);
+    rt_counts_range(a.counts, n, a.capacity, off, cnt);
     if (cnt < a.min_points) return;                                    // geo_module.py:46 (uniform per block)
     const float* k0 = a.kp0 + 2 * (size_t)off;
     const float* k1 = a.kp1 + 2 * (size_t)off;
     // ---- the 4 correspondences of hypothesis t (every lane of the group draws the same four) and row r of its 8x8 system
-    int idx[4], ok = t < a.iters;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        int found = 0;
-        for (uint32_t attempt = 0; attempt < 16 && !found && ok; ++attempt) {
-            const int c = (int)(draw(a.seed, (uint32_t)n, (uint32_t)t, (uint32_t)k, attempt) % (uint32_t)cnt);
-            int dup = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) dup |= (j < k && idx[j] == c);
-            if (!dup) { idx[k] = c; found = 1; }
-        }
-        if (!found) { ok = 0; idx[k] = 0; }
-    }
+    int idx[4];
+    int ok = gs_draw_distinct<4>(a.seed, (uint32_t)n, (uint32_t)t, cnt, idx);
+    ok = ok && t < a.iters;
     const int pt = r >> 1;
     const int ip = pt == 0 ? idx[0] : pt == 1 ? idx[1] : pt == 2 ? idx[2] : idx[3];
     const double x = (double)k0[2 * ip], y = (double)k0[2 * ip + 1], u = (double)k1[2 * ip], v = (double)k1[2 * ip + 1];
@@ -310,17 +265,17 @@ __global__ __launch_bounds__(256) void ransac_final(RsArgs a) {
     __shared__ int sh_state;
     const int n = blockIdx.x, t = threadIdx.x;
     int off, cnt;
-    rs_range(a, n, off, cnt);
+    rt_counts_range(a.counts, n, a.capacity, off, cnt);
     uint8_t* keep = a.keep + off;
     const float* k0 = a.kp0 + 2 * (size_t)off;
     const float* k1 = a.kp1 + 2 * (size_t)off;
-    // ---- best hypothesis: max count, ties -> smallest t  (key = count * 2^32 + (2^31 - t))
+    // ---- best hypothesis: most inliers, then the smallest t
     long long key = -1;
     if (cnt >= a.min_points)
         for (int i = t; i < a.iters; i += 256) {
             const int c = a.hyp_cnt[(size_t)n * a.iters + i];
             if (c >= 0) {
-                const long long kk = ((long long)c << 32) | (long long)(0x7FFFFFFF - i);
+                const long long kk = rt_key(c, i);
                 key = kk > key ? kk : key;
             }
         }
@@ -331,8 +286,7 @@ __global__ __launch_bounds__(256) void ransac_final(RsArgs a) {
         __syncthreads();
     }
     key = sh_key[0];
-    const int best_cnt = key < 0 ? -1 : (int)(key >> 32);
-    const int best_t = key < 0 ? -1 : 0x7FFFFFFF - (int)(key & 0xFFFFFFFFll);
+    const int best_cnt = rt_key_count(key), best_t = rt_key_hyp(key);
     const bool have = best_cnt >= 4;
     if (!have) {                                   // no model: every match feeds the maps (geo_module.py:77-94)
         for (int i = t; i < cnt; i += 256) keep[i] = 1;
@@ -568,7 +522,7 @@ extern "C" int gf_ransac_homography_v2(const float* mkpts0_c, const float* mkpts
         return GF_ERR_WORKSPACE;
     }
     RsArgs a;
-    a.mk0 = mkpts0_c; a.mk1 = mkpts1_c; a.counts = counts; a.N = N; a.iters = iters; a.scale = scale;
+    a.mk0 = mkpts0_c; a.mk1 = mkpts1_c; a.counts = counts; a.N = N; a.iters = iters; a.capacity = capacity; a.scale = scale;
     a.scale0 = scale0; a.scale1 = scale1; a.thr2 = (double)thr * (double)thr; a.seed = seed;
     a.kp0 = kp0; a.kp1 = kp1; a.integer_kp = integer_keypoints; a.min_points = min_points < 4 ? 4 : min_points;
     a.lm_iters = lm_iters < 0 ? 0 : lm_iters;

@@ -13,7 +13,8 @@
 //                   p^(9) (linear) .. p^(0) is walked upwards, every sign change between neighbouring critical points bisected a
 //                   FIXED number of times (PS_BISECT_LOW on the derivatives, PS_BISECT_TOP + PS_NEWTON guarded Newton steps on p).
 //                   Between -bound and +bound an even-degree polynomial changes sign an even number of times: 0, 2, .. 10 roots.
-//   ps_sampson      OpenCV's essential-matrix residual (x1^T E x0)^2 / (Ex0[0]^2 + Ex0[1]^2 + E^Tx1[0]^2 + E^Tx1[1]^2); inlier iff < thr^2.
+//   ps_inlier       OpenCV's essential-matrix residual (gs_sampson of solver_common.h) on normalised coordinates; inlier iff < thr^2.
+//                   The five matches of a hypothesis: gs_draw_distinct<5>.
 //   ps_decompose    E -> (R1, R2, t) without an SVD: t from the largest column of 1/2 tr(EE^T) I - EE^T, R = (cof(E) -+ [t]x E) / |t|^2
 //                   (Horn 1990).  Candidates in the fixed order (R1, t), (R2, t), (R1, -t), (R2, -t).
 //   ps_cheiral      a match votes for a candidate when it triangulates to a depth in (0, 1e9) in both cameras (recoverPose's
@@ -37,7 +38,6 @@
 #define PS_MAX_ROOTS 10
 #define PS_HYP_PER_WG 32          /* hypotheses one workgroup of pose_score solves: iters must be a positive multiple */
 #define PS_MIN_MATCHES 5
-#define PS_DRAW_ATTEMPTS 16
 #define PS_BISECT_LOW 40
 #define PS_BISECT_TOP 56
 #define PS_NEWTON 2
@@ -458,32 +458,8 @@ PS_HD double ps_threshold(const float* K0, const float* K1, double pixel_thr) { 
     const double f0 = (double)K0[0], f1 = (double)K1[4];
     return pixel_thr / ((((f0 + f1) + f0) + f1) / 4.0);
 }
-PS_HD double ps_sampson(const double (&E)[9], double x0, double y0, double x1, double y1) {
-    const double a0 = (E[0] * x0 + E[1] * y0) + E[2], a1 = (E[3] * x0 + E[4] * y0) + E[5], a2 = (E[6] * x0 + E[7] * y0) + E[8];
-    const double b0 = (E[0] * x1 + E[3] * y1) + E[6], b1 = (E[1] * x1 + E[4] * y1) + E[7];
-    const double num = (x1 * a0 + y1 * a1) + a2;
-    return (num * num) / (((a0 * a0 + a1 * a1) + b0 * b0) + b1 * b1);
-}
 PS_HD int ps_inlier(const double (&E)[9], double x0, double y0, double x1, double y1, double thr2) {
-    return ps_sampson(E, x0, y0, x1, y1) < thr2;                   // a NaN is never an inlier
-}
-
-// five distinct matches of hypothesis t among cnt (k_ransac's draw, re-drawn through the attempt counter)
-PS_HD int ps_draw5(uint32_t seed, uint32_t sample, uint32_t t, int cnt, int (&idx)[5]) {
-    int ok = 1;
-    PS_UNROLL
-    for (int k = 0; k < 5; ++k) {
-        int found = 0;
-        for (uint32_t attempt = 0; attempt < PS_DRAW_ATTEMPTS && !found && ok; ++attempt) {
-            const int c = (int)(draw(seed, sample, t, (uint32_t)k, attempt) % (uint32_t)cnt);
-            int dup = 0;
-            PS_UNROLL
-            for (int j = 0; j < 5; ++j) dup |= (j < k && idx[j] == c);
-            if (!dup) { idx[k] = c; found = 1; }
-        }
-        if (!found) { ok = 0; idx[k] = 0; }
-    }
-    return ok;
+    return gs_sampson(E, x0, y0, x1, y1) < thr2;                   // a NaN is never an inlier
 }
 
 // ---- pose from E

@@ -9,6 +9,10 @@
 //   gs_real_roots<D>   real roots of a polynomial of degree D without an eigen-solver: the roots of the k-th derivative separate those of
 //                      the (k-1)-th, so the chain p^(D-1) (linear) .. p^(0) is walked upwards, every sign change between neighbouring
 //                      critical points bisected a FIXED number of times, then guarded Newton steps on p itself.
+//   gs_draw_distinct<K> K distinct rows of hypothesis t of pair `sample` among cnt, from the counter-based hash of gf_hash.h: a duplicate is
+//                      drawn again through the attempt counter, GS_DRAW_ATTEMPTS times at most.
+//   gs_sampson         the squared Sampson distance of a match under a 3x3 matrix: (x1^T S x0)^2 / (Sx0[0]^2 + Sx0[1]^2 + S^Tx1[0]^2 +
+//                      S^Tx1[1]^2), OpenCV's residual for E and F alike.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -28,6 +32,8 @@
 #else
 #define GS_UNROLL
 #endif
+
+#define GS_DRAW_ATTEMPTS 16
 
 struct GsWs {
     double* p;
@@ -152,4 +158,30 @@ GS_HD int gs_real_roots(const GsWs& w, int off_p, int off_r0, int off_r1, int bi
         }
     }
     return nprev;
+}
+
+// returns 0 (and idx[k] = 0 from the first failure on) when some row stayed a duplicate after GS_DRAW_ATTEMPTS draws
+template <int K>
+GS_HD int gs_draw_distinct(uint32_t seed, uint32_t sample, uint32_t t, int cnt, int (&idx)[K]) {
+    int ok = 1;
+    GS_UNROLL
+    for (int k = 0; k < K; ++k) {
+        int found = 0;
+        for (uint32_t attempt = 0; attempt < GS_DRAW_ATTEMPTS && !found && ok; ++attempt) {
+            const int c = (int)(draw(seed, sample, t, (uint32_t)k, attempt) % (uint32_t)cnt);
+            int dup = 0;
+            GS_UNROLL
+            for (int j = 0; j < K; ++j) dup |= (j < k && idx[j] == c);
+            if (!dup) { idx[k] = c; found = 1; }
+        }
+        if (!found) { ok = 0; idx[k] = 0; }
+    }
+    return ok;
+}
+
+GS_HD double gs_sampson(const double (&S)[9], double x0, double y0, double x1, double y1) {
+    const double a0 = (S[0] * x0 + S[1] * y0) + S[2], a1 = (S[3] * x0 + S[4] * y0) + S[5], a2 = (S[6] * x0 + S[7] * y0) + S[8];
+    const double b0 = (S[0] * x1 + S[3] * y1) + S[6], b1 = (S[1] * x1 + S[4] * y1) + S[7];
+    const double num = (x1 * a0 + y1 * a1) + a2;
+    return (num * num) / (((a0 * a0 + a1 * a1) + b0 * b0) + b1 * b1);
 }

@@ -96,7 +96,7 @@ def scene(seed, n, outlier_frac=0.3):
 
 
 def sampson_px(F, p0, p1):
-    """Sampson distance in pixels (the square root of fs_sampson) of pixel matches under F"""
+    """Sampson distance in pixels (the square root of gs_sampson) of pixel matches under F"""
     x0, x1 = np.c_[p0, np.ones(len(p0))], np.c_[p1, np.ones(len(p1))]
     Fx0, Ftx1 = x0 @ F.T, x1 @ F
     num = np.sum(x1 * Fx0, 1)

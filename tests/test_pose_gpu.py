@@ -36,12 +36,15 @@ def _device(mk0, mk1, counts, iters=256, seed=0x5EED, N=None):
     return {k: v.cpu().numpy() for k, v in rs.items()}
 
 
-def test_device_equals_host_build(five_pairs):
+@pytest.mark.parametrize('iters', [32, 64, 256])
+def test_device_equals_host_build(five_pairs, iters):
+    """32 hypotheses: one workgroup per pair; 64: two; 256: eight.  The 5-match pair is the tie case - every hypothesis that solves has
+    5 inliers - so the winner must be the smallest hypothesis and its smallest root across all workgroups, as on the host."""
     scenes, mk0, mk1, counts = five_pairs
-    dev = _device(mk0, mk1, counts)
+    dev = _device(mk0, mk1, counts, iters=iters)
     off = 0
     for n, cnt in enumerate(COUNTS):
-        host = P.host_ransac(mk0[off:off + cnt], mk1[off:off + cnt], iters=256, sample=n)
+        host = P.host_ransac(mk0[off:off + cnt], mk1[off:off + cnt], iters=iters, sample=n)
         assert int(dev['valid'][n]) == host['valid'] == (1 if cnt >= 5 else 0), n
         assert tuple(dev['hypothesis'][n]) == tuple(host['hyp']), n
         assert int(dev['n_inliers'][n]) == host['n_inliers'], n
@@ -49,6 +52,40 @@ def test_device_equals_host_build(five_pairs):
         for k in ('E', 'R', 't'):                                   # bit-equal: same text, fp64, contraction off on both sides
             assert np.array_equal(dev[k][n].view(np.int64), host[k].view(np.int64)), (n, k, np.abs(dev[k][n] - host[k]).max())
         off += cnt
+
+
+def test_a_pair_depends_on_its_index_not_on_its_neighbours(five_pairs):
+    """the draw is keyed by (seed, n, t): the 130-match scene at index 2 of a 3-pair and of a 5-pair launch (index 1 empty there) gives the
+    same bits"""
+    scenes = five_pairs[0]
+    mid = scenes[1]
+    la = [scenes[2], scenes[3], mid]
+    lb = [scenes[0], None, mid, scenes[2], scenes[3]]
+    out = []
+    for lst in (la, lb):
+        cnts = [0 if s is None else len(s['mk0']) for s in lst]
+        mk0 = np.concatenate([s['mk0'] for s in lst if s is not None])
+        mk1 = np.concatenate([s['mk1'] for s in lst if s is not None])
+        dev = _device(mk0, mk1, np.array([sum(cnts), *cnts], np.int32))
+        off = sum(cnts[:2])
+        out.append({**{k: dev[k][2] for k in ('E', 'R', 't', 'valid', 'n_inliers', 'hypothesis')}, 'inliers': dev['inliers'][off:off + cnts[2]]})
+    assert out[0]['valid'] == 1 and len(out[0]['inliers']) == COUNTS[1]
+    for k in out[0]:
+        assert np.array_equal(out[0][k], out[1][k]), k
+
+
+def test_argument_errors_launch_nothing():
+    from geoformer_amd import _lib
+    h = _lib.lib()
+    buf = torch.zeros(1 << 18, dtype=torch.uint8, device=DEV)
+    p = buf.data_ptr()
+
+    def call(N, iters, ws_bytes):
+        return h.gf_pose_essential_ransac(p, p, p, N, 64, p, p, 0.5, iters, 1, p, p, p, p, p, p, p, p, ws_bytes, None)
+    assert call(0, 256, 1 << 18) == -1 and b'need N' in h.gf_last_error()
+    need = h.gf_pose_workspace_bytes(2, 256)
+    assert 0 < need <= 1 << 18 and h.gf_pose_workspace_bytes(0, 256) == 0
+    assert call(2, 256, need - 1) == -2 and b'workspace too small' in h.gf_last_error()
 
 
 def test_device_recovers_the_planted_pose(five_pairs):
