@@ -72,6 +72,13 @@ struct LinArgs {
     // (r / rm_w) * rm_line + (r % rm_w) * rm_pix instead of r * lda1; rm_w == 0: off
     int rm_w;
     long rm_line, rm_pix;
+    // row-address table of the A operand (AROWS instances; k2 == 0): row r of the product reads the K elements at address rows[r] instead of
+    // a1 + r * lda1; 0: a row of zeros
+    const unsigned long long* rows;
+    // AROWS, counts that live on the device (gf_linear_rows' group_count; null: off): the rows come in groups of grp_rows, and the rows at or
+    // beyond grp_count[g * grp_stride] in group g are don't-care - a tile that holds no other row exits at once, its output rows stay unwritten
+    const int32_t* grp_count;
+    int grp_stride, grp_rows;
 };
 
 // Tile of a workgroup.  Linear workgroup ids go round-robin over the 8 XCDs (= 8 L2s); with the grid's native order the column
@@ -91,7 +98,8 @@ __device__ __forceinline__ void lin_tile(int& row_tile, int& col_tile) {
 
 // CONVX: the forms the backbone's 1x1 convolutions need (compiled only into their instances: the matching path's kernels keep their
 // register budget) - K not a multiple of the K step, and the strided-pixel row map of LinArgs
-template <typename T, int NB, int EPI, bool CONVX = false>
+// AROWS: the A rows are named by LinArgs::rows (gf_linear_rows) - likewise compiled only into its own instances
+template <typename T, int NB, int EPI, bool CONVX = false, bool AROWS = false>
 __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void linear_kernel(LinArgs a) {
     using Mm = Mma32<T>;
     using Frag = typename Mm::Frag;
@@ -109,6 +117,15 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void linear_kernel(Lin
     lin_tile(row_tile, col_tile);
     const int m0 = row_tile * 128, n0 = col_tile * WROWS;
     const int K = a.k1 + a.k2;
+    if constexpr (AROWS) {
+        if (a.grp_count) {                            // uniform: the whole workgroup leaves, before its first barrier
+            bool needed = false;
+            const int mend = min(m0 + 128, a.M);
+            for (int g = m0 / a.grp_rows, r = m0; r < mend && !needed; r = ++g * a.grp_rows)      // r: the tile's first row in group g
+                needed = r - g * a.grp_rows < a.grp_count[(size_t)g * a.grp_stride];
+            if (!needed) return;
+        }
+    }
 
     if (tid < WROWS) {
         vec[tid] = (a.bias && n0 + tid < a.N) ? a.bias[n0 + tid] : 0.f;
@@ -127,6 +144,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void linear_kernel(Lin
         isa[p] = row < 128;
         if (isa[p]) {
             src[p] = nullptr;                      // resolved per K step (two-part operand)
+            if constexpr (AROWS) src[p] = reinterpret_cast<const T*>(a.rows[min(m0 + row, a.M - 1)]);   // the row's address, read once; null: zeros
             dst[p] = gf_lds_off(row, c);
         } else {
             const int wr = row - 128;
@@ -148,11 +166,21 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void linear_kernel(Lin
             const int e = p * 256 + tid, row = e >> 3, c = e & 7;
             const T* g;
             if (isa[p]) {
-                const int r = min(m0 + row, a.M - 1);
-                const size_t ro = (CONVX && a.rm_w > 0) ? (size_t)(r / a.rm_w) * a.rm_line + (size_t)(r % a.rm_w) * a.rm_pix : (size_t)r * ld;
-                g = ab + ro + kk + c * EPC;
+                if constexpr (AROWS) {
+                    g = src[p] + k0 + c * EPC;
+                } else {
+                    const int r = min(m0 + row, a.M - 1);
+                    const size_t ro = (CONVX && a.rm_w > 0) ? (size_t)(r / a.rm_w) * a.rm_line + (size_t)(r % a.rm_w) * a.rm_pix : (size_t)r * ld;
+                    g = ab + ro + kk + c * EPC;
+                }
             } else {
                 g = src[p] + k0;
+            }
+            if constexpr (AROWS) {
+                if (isa[p] && src[p] == nullptr) {
+                    regs[p] = v4u{0u, 0u, 0u, 0u};
+                    continue;
+                }
             }
             if (!ragged || k0 + c * EPC < K) regs[p] = *reinterpret_cast<const v4u*>(g);
             else regs[p] = v4u{0u, 0u, 0u, 0u};
@@ -525,22 +553,22 @@ __global__ __launch_bounds__(256, 2) void linear_kernel_w2(LinArgs a) {
     }
 }
 
-template <typename T, int NB, int EPI, bool CONVX = false>
+template <typename T, int NB, int EPI, bool CONVX = false, bool AROWS = false>
 void lin_launch1(const LinArgs& a, hipStream_t st) {
     constexpr int WROWS = 32 * NB;
     size_t lds = (size_t)(128 + WROWS) * 128 + 3 * WROWS * sizeof(float);
     if (lds < 4 * 32 * 272) lds = 4 * 32 * 272;                          // fp16 epilogue slabs
-    linear_kernel<T, NB, EPI, CONVX><<<dim3((a.M + 127) / 128, (a.N + WROWS - 1) / WROWS), 256, lds, st>>>(a);
+    linear_kernel<T, NB, EPI, CONVX, AROWS><<<dim3((a.M + 127) / 128, (a.N + WROWS - 1) / WROWS), 256, lds, st>>>(a);
 }
 
-template <typename T, int NB>
+template <typename T, int NB, bool AROWS = false>
 void lin_launch(const LinArgs& a, int epi, hipStream_t st) {
     switch (epi) {
-        case EPI_NONE: lin_launch1<T, NB, EPI_NONE>(a, st); break;
-        case EPI_RELU: lin_launch1<T, NB, EPI_RELU>(a, st); break;
-        case EPI_TANH: lin_launch1<T, NB, EPI_TANH>(a, st); break;
-        case EPI_LN: lin_launch1<T, NB, EPI_LN>(a, st); break;
-        default: lin_launch1<T, NB, EPI_LN_RES>(a, st); break;
+        case EPI_NONE: lin_launch1<T, NB, EPI_NONE, false, AROWS>(a, st); break;
+        case EPI_RELU: lin_launch1<T, NB, EPI_RELU, false, AROWS>(a, st); break;
+        case EPI_TANH: lin_launch1<T, NB, EPI_TANH, false, AROWS>(a, st); break;
+        case EPI_LN: lin_launch1<T, NB, EPI_LN, false, AROWS>(a, st); break;
+        default: lin_launch1<T, NB, EPI_LN_RES, false, AROWS>(a, st); break;
     }
 }
 
@@ -602,6 +630,76 @@ extern "C" int gf_linear(const void* a1, long lda1, int k1, const void* a2, long
         else lin_launch<gf_bf16, 4>(a, epilogue, st);
     }
     gf_prof_end("k3_linear", pt, st);
+    GF_CHECK_LAUNCH();
+    return GF_OK;
+}
+
+// gf_linear with the A operand given as a device table of M row addresses (a gather fused into the operand staging: FinePreprocess's window
+// and coarse rows are read where they lie).  Same tile walk, K loop and epilogues as gf_linear - always through linear_kernel, whose
+// accumulation order linear_kernel_w2 shares: the bits of gf_linear on the rows copied into a buffer.
+extern "C" int gf_linear_rows(const uint64_t* row_table, int row_align, const int32_t* group_count, int group_count_stride, int group_rows,
+                              int k, const void* w, const float* bias, const void* rowgroup_bias, int rowgroup_rows, int epilogue,
+                              const float* ln_gamma, const float* ln_beta, float ln_eps, const void* residual, long ldres,
+                              const int32_t* row_flag, int flag_rows, void* out, long ldo, int dtype, int M, int N, void* stream) {
+    GF_CHECK_ARG(row_table && w && out, "null pointer");
+    GF_CHECK_ARG(dtype == GF_F16 || dtype == GF_BF16, "built for the 16-bit types (fp32: gf_linear on a gathered copy)");
+    GF_CHECK_ARG(M > 0 && N > 0 && k > 0, "bad sizes");
+    GF_CHECK_ARG(k % 64 == 0, "k must be a multiple of 64");
+    GF_CHECK_ARG(N % 32 == 0, "N must be a multiple of 32");
+    GF_CHECK_ARG(epilogue >= EPI_NONE && epilogue <= EPI_LN_RES, "unknown epilogue");
+    GF_CHECK_ARG(rowgroup_bias == nullptr || rowgroup_rows > 0, "rowgroup_rows must be > 0");
+    GF_CHECK_ARG(row_align > 0 && (row_align & (row_align - 1)) == 0 && row_align % 16 == 0, "operand rows must be 16-byte aligned (row_align: a power of two >= 16)");
+    GF_CHECK_ARG((uintptr_t)row_table % 8 == 0, "the row table must be 8-byte aligned");
+    GF_CHECK_ARG(group_count == nullptr || (group_rows > 0 && group_count_stride >= 0), "group_rows must be > 0");
+    GF_CHECK_ARG((ldo * 2) % 16 == 0 && (uintptr_t)out % 16 == 0, "output rows must be 16-byte aligned");
+    GF_CHECK_ARG(residual == nullptr || ((ldres * 2) % 16 == 0 && (uintptr_t)residual % 16 == 0), "residual rows must be 16-byte aligned");
+    if (epilogue >= EPI_LN) {
+        GF_CHECK_ARG(ln_gamma && ln_beta, "LayerNorm epilogue needs gamma and beta");
+        GF_CHECK_ARG(N == 128 || N == 256, "LayerNorm epilogue is built for N = 128 or 256 (whole rows per wave pair)");
+        GF_CHECK_ARG(epilogue != EPI_LN_RES || residual != nullptr, "residual missing");
+        GF_CHECK_ARG(row_flag == nullptr || flag_rows > 0, "flag_rows must be > 0");
+    }
+    LinArgs a{nullptr, nullptr, 0, 0, k, 0, w, bias, rowgroup_bias, rowgroup_rows, ln_gamma, ln_beta, ln_eps, residual,
+              ldres, row_flag, flag_rows, out, ldo, M, N};
+    a.rows = (const unsigned long long*)row_table;
+    a.grp_count = group_count; a.grp_stride = group_count_stride; a.grp_rows = group_rows;
+    hipStream_t st = (hipStream_t)stream;
+    // declared work as in gf_linear (algorithmic bytes) plus the table.  With counts on the device the host does not know how many rows are
+    // computed: only the bytes that move whatever the counts are declared (weights + table) - a lower bound, so the k3_linear roofline
+    // figure can only come out lower for these launches, never flattered by rows that were skipped
+    const double rows_moved = group_count ? 0.0 : (double)M;
+    void* pt = gf_prof_begin("k3_linear", st, 2.0 * (rows_moved * k + (double)N * k + rows_moved * N * (residual ? 2.0 : 1.0)) + 8.0 * M);
+    const bool wide = (epilogue >= EPI_LN) ? N == 256 : N % 256 == 0;
+    if (dtype == GF_F16) {
+        if (wide) lin_launch<_Float16, 8, true>(a, epilogue, st);
+        else lin_launch<_Float16, 4, true>(a, epilogue, st);
+    } else {
+        if (wide) lin_launch<gf_bf16, 8, true>(a, epilogue, st);
+        else lin_launch<gf_bf16, 4, true>(a, epilogue, st);
+    }
+    gf_prof_end("k3_linear", pt, st);
+    GF_CHECK_LAUNCH();
+    return GF_OK;
+}
+
+// The row table of a token list: rows[n][j] = the address of row idx[n][j] (clamped into [0, L)) of sample n of x [N][L] rows of row_bytes bytes
+// (GeoTransformer's self layers: the tokens at inlier cells, whose k | v projection gf_linear_rows then computes - and no other token's).
+namespace {
+__global__ __launch_bounds__(256) void index_rows_kernel(const char* x, long row_bytes, const int32_t* idx, long idx_stride, int N, int L,
+                                                         unsigned long long* rows) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (long)N * L) return;
+    const long n = e / L, j = e - n * L;
+    const int t = min(max(idx[n * idx_stride + j], 0), L - 1);
+    rows[e] = (unsigned long long)(uintptr_t)(x + (n * L + t) * row_bytes);
+}
+}   // namespace
+
+extern "C" int gf_index_rows(const void* x, long row_bytes, const int32_t* idx, long idx_stride, int N, int L, uint64_t* rows, void* stream) {
+    GF_CHECK_ARG(x && idx && rows, "null pointer");
+    GF_CHECK_ARG(N > 0 && L > 0 && (long)N * L < (1l << 31) && row_bytes > 0 && idx_stride >= 0, "bad sizes");
+    index_rows_kernel<<<(unsigned)(((long)N * L + 255) / 256), 256, 0, (hipStream_t)stream>>>((const char*)x, row_bytes, idx, idx_stride, N, L,
+                                                                                              (unsigned long long*)rows);
     GF_CHECK_LAUNCH();
     return GF_OK;
 }

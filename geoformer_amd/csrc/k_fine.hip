@@ -122,6 +122,50 @@ __global__ __launch_bounds__(256) void fine_gather_rows(FgArgs<Src> a) {
     for (int c8 = lane * 8; c8 < a.CC; c8 += 512) *reinterpret_cast<v4u*>(co + c8) = *reinterpret_cast<const v4u*>(cf + c8);
 }
 
+// The 16-bit entry without the copy (maps already of the compute type, channels-last): the window rows are NAMED, not moved.  One wave per
+// (match, side) writes the addresses of its W x W taps' channel rows - 0 where fine_gather_rows writes zeros: a tap outside the sample's own
+// extent - and of its coarse feature row; gf_linear_rows (k3_linear.hip) then reads the rows where they lie.  Element size 2 for every type.
+template <typename Src>
+struct FrArgs {
+    Src f0, f1;
+    const void* c0;          // coarse (geo) features [N, L, CC], [N, S, CC]
+    const void* c1;
+    int L, S, CC;
+    const int64_t* b_ids;
+    const int64_t* i_ids;
+    const int64_t* j_ids;
+    int M, w0c, w1c, stride, W;
+    unsigned long long* win_rows;   // [2M][W*W]  (image0 windows first, then image1)
+    unsigned long long* c_rows;     // [2M]
+};
+
+template <typename Src>
+__global__ __launch_bounds__(256) void fine_row_table(FrArgs<Src> a) {
+    using E = unsigned short;
+    const int lane = threadIdx.x & 63, u = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+    if (u >= 2 * a.M) return;
+    const int side = u >= a.M, m = side ? u - a.M : u;
+    const int b = (int)a.b_ids[m];
+    const int cell = (int)(side ? a.j_ids[m] : a.i_ids[m]);
+    const int wc = side ? a.w1c : a.w0c;
+    const GfMapView<E> f = (side ? a.f1 : a.f0).template view<E>(b);
+    const int cy = (cell / wc) * a.stride - a.W / 2, cx = (cell % wc) * a.stride - a.W / 2;
+    for (int k = lane; k < a.W * a.W; k += 64) {
+        const int y = cy + k / a.W, x = cx + k % a.W;
+        unsigned long long p = 0ull;
+        if (y >= 0 && y < f.h && x >= 0 && x < f.w) p = (unsigned long long)(uintptr_t)(f.base + y * f.sh + x * f.sw);
+        a.win_rows[(size_t)u * a.W * a.W + k] = p;
+    }
+    if (lane == 0) a.c_rows[u] = (unsigned long long)(uintptr_t)((const E*)(side ? a.c1 : a.c0) + ((size_t)b * (side ? a.S : a.L) + cell) * a.CC);
+}
+
+template <typename Src>
+int fr_launch(const FrArgs<Src>& a, void* stream) {
+    fine_row_table<Src><<<(2 * a.M + 3) / 4, 256, 0, (hipStream_t)stream>>>(a);
+    GF_CHECK_LAUNCH();
+    return GF_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 struct FmArgs {
     const void* f0;          // [M][WW][C]
@@ -424,6 +468,50 @@ extern "C" int gf_fine_gather_ragged(const gf_map_record* f0_table, const gf_map
     FG_CHECK_ARGS(f0_table && f1_table, N > 0, N <= 65535, feat_align);
     FgArgs<GfRaggedMaps> a{{f0_table}, {f1_table}, FG_COMMON_ARGS};
     return fg_dispatch(feat_dtype, dtype, a, stream, feat_align);
+}
+
+// The three gf_fine_rows entries: the checks in one order, as above.  rows_ok: what the entry knows about its maps' channel rows (contiguous,
+// 16-byte aligned); a ragged table's records are the caller's promise.
+#define FR_CHECK_ARGS(maps_ok, n_ok, rows_ok)                                                                                              \
+    GF_CHECK_ARG((maps_ok) && feat_c0 && feat_c1 && b_ids && i_ids && j_ids && win_rows && coarse_rows, "null pointer");                   \
+    GF_CHECK_ARG(n_ok, "empty table");                                                                                                     \
+    GF_CHECK_ARG(M > 0 && (long)M * window * window < (1l << 30), "M must be > 0 and 2 M window^2 < 2^31");                                \
+    GF_CHECK_ARG(window > 0 && stride > 0 && w0c > 0 && w1c > 0 && CC > 0, "bad sizes");                                                   \
+    GF_CHECK_ARG(rows_ok, "channel rows must be contiguous and 16-byte aligned (channels-last maps, strides multiples of 8 elements)");    \
+    GF_CHECK_ARG((uintptr_t)feat_c0 % 16 == 0 && (uintptr_t)feat_c1 % 16 == 0 && CC % 8 == 0, "coarse rows must be 16-byte aligned")
+#define FR_COMMON_ARGS feat_c0, feat_c1, L, S, CC, b_ids, i_ids, j_ids, M, w0c, w1c, stride, window, (unsigned long long*)win_rows, (unsigned long long*)coarse_rows
+#define FR_STRIDES_OK(s) ((s)[0] == 1 && (s)[1] % 8 == 0 && (s)[2] % 8 == 0)
+
+extern "C" int gf_fine_rows(const void* feat_f0, const void* feat_f1, const long* strides0, const long* strides1, int H0, int W0, int H1,
+                            int W1, const void* feat_c0, const void* feat_c1, int L, int S, int CC, const int64_t* b_ids,
+                            const int64_t* i_ids, const int64_t* j_ids, int M, int w0c, int w1c, int stride, int window,
+                            uint64_t* win_rows, uint64_t* coarse_rows, void* stream) {
+    FR_CHECK_ARGS(feat_f0 && feat_f1 && strides0 && strides1, true,
+                  strides0[0] % 8 == 0 && strides1[0] % 8 == 0 && FR_STRIDES_OK(strides0 + 1) &&
+                      FR_STRIDES_OK(strides1 + 1) && (uintptr_t)feat_f0 % 16 == 0 && (uintptr_t)feat_f1 % 16 == 0);
+    FrArgs<GfTensorMaps> a{{feat_f0, strides0[0], strides0[1], strides0[2], strides0[3], H0, W0},
+                           {feat_f1, strides1[0], strides1[1], strides1[2], strides1[3], H1, W1}, FR_COMMON_ARGS};
+    return fr_launch(a, stream);
+}
+
+extern "C" int gf_fine_rows_ptrs(const void* const* f0_table, const void* const* f1_table, int N, int feat_align, const long* strides0,
+                                 const long* strides1, int H0, int W0, int H1, int W1, const void* feat_c0, const void* feat_c1, int L,
+                                 int S, int CC, const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids, int M, int w0c, int w1c,
+                                 int stride, int window, uint64_t* win_rows, uint64_t* coarse_rows, void* stream) {
+    FR_CHECK_ARGS(f0_table && f1_table && strides0 && strides1, N > 0,
+                  FR_STRIDES_OK(strides0) && FR_STRIDES_OK(strides1) && feat_align > 0 && feat_align % 16 == 0);
+    FrArgs<GfTableMaps> a{{f0_table, strides0[0], strides0[1], strides0[2], H0, W0},
+                          {f1_table, strides1[0], strides1[1], strides1[2], H1, W1}, FR_COMMON_ARGS};
+    return fr_launch(a, stream);
+}
+
+extern "C" int gf_fine_rows_ragged(const gf_map_record* f0_table, const gf_map_record* f1_table, int N, int feat_align, const void* feat_c0,
+                                   const void* feat_c1, int L, int S, int CC, const int64_t* b_ids, const int64_t* i_ids,
+                                   const int64_t* j_ids, int M, int w0c, int w1c, int stride, int window, uint64_t* win_rows,
+                                   uint64_t* coarse_rows, void* stream) {
+    FR_CHECK_ARGS(f0_table && f1_table, N > 0, feat_align > 0 && feat_align % 16 == 0);
+    FrArgs<GfRaggedMaps> a{{f0_table}, {f1_table}, FR_COMMON_ARGS};
+    return fr_launch(a, stream);
 }
 
 extern "C" size_t gf_fine_match_workspace_bytes(int M) {

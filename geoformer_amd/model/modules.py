@@ -127,6 +127,14 @@ class LoFTREncoderLayer(nn.Module):
         c = self.d_model
         return kv[..., :c], kv[..., c:]
 
+    def project_kv_at(self, x, idx, counts):
+        """k and v of the listed tokens only (16-bit modes): x [N, L, C], idx int32 [N, >= L], counts int32 [N] on the device -> views
+        of a compact [N, L, 2C] buffer whose row (n, j) is the projection of token idx[n, j].  Rows at or beyond counts[n] are
+        don't-care: whole 128-row tiles of them are never computed (ops.linear_rows' group_count) and stay unwritten."""
+        kv = ops.linear_rows(ops.index_rows(x, idx), self.weights(x.dtype)['kv'], group_count=counts)
+        c = self.d_model
+        return kv[..., :c], kv[..., c:]
+
     def project_qkv(self, x):
         """q, k and v of the SAME tokens in one GEMM (x read once, one launch): row-strided views of a [..., 3C] tensor."""
         qkv = ops.linear(x, self.weights(x.dtype)['qkv'])
@@ -396,6 +404,19 @@ class GeoTransformer(nn.Module):
             if p.dim() > 1:
                 nn.init.xavier_uniform_(p)
         self.norm = nn.LayerNorm(d_model)         # present in the checkpoint, never applied (:144-145)
+        self.kv_at_inliers = True                 # self layers, 16-bit modes: k | v projected at the inlier tokens only (False: at every token)
+        self._ident = {}
+
+    def _identity(self, N, L, device):
+        """The token list 0 .. L-1, one row shared by every sample (row stride 0): K4's list for a k / v buffer already in list order.
+        Made once per (L, device) and kept.  A first call that falls INSIDE a stream capture makes a list of its own that is not kept: it
+        lives in that graph's memory pool and is filled by the graph's replays, so no other call may be handed it."""
+        t = self._ident.get((L, device))
+        if t is None:
+            t = torch.arange(L, dtype=torch.int32, device=device)
+            if not torch.cuda.is_current_stream_capturing():
+                self._ident[(L, device)] = t
+        return t.unsqueeze(0).expand(N, L)
 
     def forward(self, feat0, feat1, geo, both: Optional[torch.Tensor] = None):
         """feat0 [N,L,C], feat1 [N,S,C]; geo = dict(idx0, idx1, nidx, win0, win1, valid) on the device:
@@ -413,8 +434,15 @@ class GeoTransformer(nn.Module):
         for layer, name in zip(self.layers, self.layer_names):
             if name == 'self':       # keys/values = tokens at inlier cells; a sample without any keeps its features
                 if same:
-                    q, k, v = layer.project_qkv(both)
-                    msg = ops.self_attention_gathered(q, k, v, geo['idx_both'], geo['nidx_both'], self.nhead)
+                    if self.kv_at_inliers and both.dtype != torch.float32 and both.is_contiguous() and both.data_ptr() % 16 == 0:
+                        # K4 reads k and v at the inlier tokens only (a fifth of the map at the nominal load): project exactly those,
+                        # compactly and in list order - K4 then walks them with the identity list.  Same values, same key order.
+                        q = layer.project_q(both)
+                        k, v = layer.project_kv_at(both, geo['idx_both'], geo['nidx_both'])
+                        msg = ops.self_attention_gathered(q, k, v, self._identity(2 * n, L, both.device), geo['nidx_both'], self.nhead)
+                    else:
+                        q, k, v = layer.project_qkv(both)
+                        msg = ops.self_attention_gathered(q, k, v, geo['idx_both'], geo['nidx_both'], self.nhead)
                     both = layer.finish(both, msg, geo['nidx_both'], L)
                     feat0, feat1 = both[:n], both[n:]
                 else:
@@ -579,11 +607,26 @@ class FinePreprocess(nn.Module):
         if M == 0:
             e = torch.empty(0, W ** 2, self.d_model_f, device=feat_f0.device, dtype=dtype)
             return e, e.clone()
-        win, ccat = ops.fine_gather(feat_f0, feat_f1, feat_c0, feat_c1, data['b_ids'], data['i_ids'], data['j_ids'],
-                                    int(data['hw0_c'][1]), int(data['hw1_c'][1]), stride, W, dtype)
         w = self.weights(dtype)
+        ids = (data['b_ids'], data['i_ids'], data['j_ids'], int(data['hw0_c'][1]), int(data['hw1_c'][1]), stride, W)
         # merge_feat(cat([win, down_proj(c)])) = W_win.win + (W_ctx.down_proj(c) + b): the context term is
         # computed once per match and enters the window GEMM as a row-group bias (25 rows per match)
+        #
+        # Maps already of the compute dtype and channels-last, a named row exactly the K elements its GEMM reads: the window and coarse
+        # rows are read where they lie - one launch writes their addresses, the two GEMMs gather through them (same bits as the copies
+        # of the other path, which are never made)
+        rows16 = (feat_f0.shape[1] == w['mw_win'].shape[1] and feat_c0.shape[-1] == feat_c1.shape[-1] == w['dw'].shape[1]
+                  and ops.fine_rows_supported(feat_f0, feat_f1, dtype))
+        if rows16:
+            fc0, fc1 = feat_c0.contiguous(), feat_c1.contiguous()          # named by the table: alive until the GEMMs are enqueued
+            rows16 = fc0.data_ptr() % 16 == 0 and fc1.data_ptr() % 16 == 0 and fc0.shape[-1] % 64 == 0
+        if rows16:
+            win_rows, c_rows = ops.fine_rows(feat_f0, feat_f1, fc0, fc1, *ids, supported=True)
+            ctx = ops.linear(ops.linear_rows(c_rows, w['dw'], bias=w['db']), w['mw_ctx'], bias=w['mb'])
+            out = ops.linear_rows(win_rows, w['mw_win'], rowgroup_bias=ctx, rowgroup_rows=W * W)
+            return out[:M], out[M:]
+        # converting modes (bf16 maps -> fp16 windows), fp32, maps that are not channels-last: gather (and convert) into win / ccat first
+        win, ccat = ops.fine_gather(feat_f0, feat_f1, feat_c0, feat_c1, *ids, dtype)
         ctx = ops.linear(ops.linear(ccat, w['dw'], bias=w['db']), w['mw_ctx'], bias=w['mb'])
         out = ops.linear(win, w['mw_win'], rowgroup_bias=ctx, rowgroup_rows=W * W)
         return out[:M], out[M:]

@@ -768,6 +768,68 @@ def fine_gather(feat_f0, feat_f1, feat_c0, feat_c1, b_ids, i_ids, j_ids, w0c, w1
     return win, ccat
 
 
+def _map_kind(feat_f0, feat_f1, what):
+    kind0, kind1 = (RaggedMapBatch if isinstance(f, RaggedMapBatch) else MapBatch if isinstance(f, MapBatch) else None for f in (feat_f0, feat_f1))
+    if kind0 is not kind1:
+        raise TypeError(f'{what}: feat_f0 and feat_f1 must both be tensors, both be MapBatches or both be RaggedMapBatches')
+    return kind0
+
+
+def fine_rows_supported(feat_f0, feat_f1, dtype):
+    """Can `fine_rows` name the window rows of these maps for a `linear_rows` in `dtype`?  16-bit maps of that very dtype (nothing to
+    convert) whose channel rows are contiguous and 16-byte aligned: channels-last, every other stride a multiple of 8 elements.  Decided
+    from what the host knows (dtypes, strides, addresses): no device synchronisation."""
+    kind = _map_kind(feat_f0, feat_f1, 'fine_rows')
+    if dtype not in (torch.float16, torch.bfloat16) or feat_f0.dtype != dtype or feat_f1.dtype != dtype or feat_f0.shape[1] % 64:
+        return False
+    for f in (feat_f0, feat_f1):
+        if kind is None:
+            ok = f.data_ptr() % 16 == 0 and f.stride(1) == 1 and all(s % 8 == 0 for s in (f.stride(0), f.stride(2), f.stride(3)))
+        elif kind is MapBatch:
+            ok = f.align >= 16 and f.map_stride[0] == 1 and f.map_stride[1] % 8 == 0 and f.map_stride[2] % 8 == 0
+        else:
+            ok = f.align >= 16 and all(m.stride(0) == 1 and m.stride(1) % 8 == 0 and m.stride(2) % 8 == 0 for m in f.maps)
+        if not ok:
+            return False
+    return True
+
+
+def fine_rows(feat_f0, feat_f1, feat_c0, feat_c1, b_ids, i_ids, j_ids, w0c, w1c, stride, window, supported=None):
+    """The K7 gather as address tables for `linear_rows` (gf_fine_rows and its siblings; `fine_rows_supported` says when): the arguments of
+    `fine_gather` -> (win_rows int64 [2M, W*W], coarse_rows int64 [2M]): the address of every window tap's channel row in the fine maps
+    (0 where fine_gather writes zeros) and of the coarse feature rows.  feat_c* must be contiguous and, like the maps, outlive the
+    launches that read the tables.  supported: `fine_rows_supported`'s answer for these maps, where the caller has asked already."""
+    kind = _map_kind(feat_f0, feat_f1, 'fine_rows')
+    if not (fine_rows_supported(feat_f0, feat_f1, feat_f0.dtype) if supported is None else supported):
+        raise ValueError('fine_rows: the maps need 16-bit, contiguous, 16-byte aligned channel rows (fine_rows_supported)')
+    if not (feat_c0.is_contiguous() and feat_c1.is_contiguous()) or feat_c0.element_size() != 2 or feat_c1.element_size() != 2:
+        raise ValueError('fine_rows: the coarse features must be contiguous 16-bit tensors')
+    if kind is not None and len(feat_f0) != len(feat_f1):
+        raise ValueError(f'fine_rows: {len(feat_f0)} maps on side 0, {len(feat_f1)} on side 1')
+    _need_cuda(*(feat_f0.maps + feat_f1.maps if kind is not None else (feat_f0, feat_f1)), feat_c0, feat_c1, b_ids)
+    M = b_ids.shape[0]
+    dev = feat_f0.device
+    win_rows = torch.empty(2 * M, window * window, dtype=torch.int64, device=dev)
+    c_rows = torch.empty(2 * M, dtype=torch.int64, device=dev)
+    ids = [_contig(t) for t in (b_ids, i_ids, j_ids)]
+    L_ = _lib.lib()
+    rest = (_p(feat_c0), _p(feat_c1), feat_c0.shape[1], feat_c1.shape[1], feat_c0.shape[-1], *map(_p, ids), M, int(w0c), int(w1c), int(stride),
+            int(window), _p(win_rows), _p(c_rows), _stream())
+    if kind is RaggedMapBatch:
+        check(L_.gf_fine_rows_ragged(_p(feat_f0.table()), _p(feat_f1.table()), len(feat_f0), min(feat_f0.align, feat_f1.align), *rest),
+              'gf_fine_rows_ragged')
+        return win_rows, c_rows
+    strides = [feat.map_stride if kind is MapBatch else feat.stride() for feat in (feat_f0, feat_f1)]
+    s0, s1 = ((ctypes.c_long * len(st))(*st) for st in strides)
+    geom = (ctypes.cast(s0, ctypes.c_void_p), ctypes.cast(s1, ctypes.c_void_p), *feat_f0.shape[2:], *feat_f1.shape[2:])
+    if kind is MapBatch:
+        check(L_.gf_fine_rows_ptrs(_p(feat_f0.table()), _p(feat_f1.table()), len(feat_f0), min(feat_f0.align, feat_f1.align), *geom, *rest),
+              'gf_fine_rows_ptrs')
+    else:
+        check(L_.gf_fine_rows(_p(feat_f0), _p(feat_f1), *geom, *rest), 'gf_fine_rows')
+    return win_rows, c_rows
+
+
 def fine_match(f0, f1, temperature, thr, b_ids, mkpts0_c, mkpts1_c, coarse_scale, c2f_scale, fine_scale, scale0=None,
                scale1=None):
     """K8.  f0, f1 [M,25,C] (M > 0) -> dict(fine_matrix [M,25,25], mkpts0_f/mkpts1_f [M,2] (first count rows
@@ -835,6 +897,52 @@ def linear(a1, w, a2=None, bias=None, rowgroup_bias=None, rowgroup_rows=0, epilo
     check(_lib.lib().gf_linear(_p(a1), lda1, k1, _p(a2), lda2, k2, _p(w), _p(bias), _p(rowgroup_bias), int(rowgroup_rows),
                                int(epilogue), _p(g), _p(b), float(eps), _p(res), ldres, _p(row_flag), int(flag_rows), _p(out),
                                N, _dt(a1), M, N, _stream()), 'gf_linear')
+    return out
+
+
+def index_rows(x, idx):
+    """The row table of a token list (gf_index_rows): x [N, L, C] with contiguous rows and batch stride L * row stride, idx int32 [N, >= L]
+    -> int64 [N, L], entry (n, j) the address of x[n, clamp(idx[n, j], 0, L - 1)].  x must outlive the launches that read the table."""
+    _need_cuda(x, idx)
+    N, L, _ = x.shape
+    ld = x.stride(1)
+    if x.stride(2) != 1 or x.stride(0) != ld * L or idx.dtype != torch.int32 or idx.shape[0] != N or idx.shape[1] < L or idx.stride(1) != 1:
+        raise ValueError('index_rows: x needs batch stride == L * row stride, idx int32 [N, >= L] with contiguous rows')
+    rows = torch.empty(N, L, dtype=torch.int64, device=x.device)
+    check(_lib.lib().gf_index_rows(_p(x), ld * x.element_size(), _p(idx), idx.stride(0), N, L, _p(rows), _stream()), 'gf_index_rows')
+    return rows
+
+
+def linear_rows(rows, w, row_align=16, bias=None, rowgroup_bias=None, rowgroup_rows=0, epilogue=EPI_NONE, ln=None, eps=1e-5,
+                residual=None, row_flag=None, flag_rows=0, out=None, group_count=None):
+    """K3 on gathered rows without the gather (gf_linear_rows): `rows` is a contiguous int64 device tensor [...] of row addresses - each
+    names w.shape[1] contiguous elements of w's dtype (fp16 or bf16), 16-byte aligned; 0 names a row of zeros - and the result
+    [..., N] has the bits of `linear` on those rows copied into a tensor.  row_align: the caller's promise - a power of two (bytes)
+    that divides every non-zero address, at least 16; the table lies in device memory and is not inspected, the value selects nothing
+    (a caller who cannot promise 16 gets an error instead of misaligned loads).  The rows must stay allocated and unchanged until the launch has run.  Other arguments as in `linear`.
+    group_count: int32 device view with one entry per rows[g] (rows [G, R]: G groups of R rows; any stride): only the first
+    group_count[g] rows of group g are wanted - a 128-row tile without a wanted row is skipped and its output rows stay unwritten."""
+    _need_cuda(rows, w)
+    if rows.dtype != torch.int64 or not rows.is_contiguous():
+        raise ValueError('linear_rows: rows must be a contiguous int64 tensor of addresses')
+    if w.dim() != 2 or not w.is_contiguous():
+        raise ValueError('linear_rows: w must be a contiguous [N, K] tensor')
+    N, k = w.shape
+    M = rows.numel()
+    if out is None:
+        out = torch.empty(*rows.shape, N, dtype=w.dtype, device=w.device)
+    elif out.shape != (*rows.shape, N) or out.dtype != w.dtype or not out.is_contiguous():
+        raise ValueError('out must be a contiguous tensor of the result shape and dtype')
+    res, ldres = (None, 0) if residual is None else _rows2d(residual)
+    g, b = (None, None) if ln is None else ln
+    gstride = grows = 0
+    if group_count is not None:
+        if rows.dim() != 2 or group_count.dtype != torch.int32 or group_count.numel() != rows.shape[0]:
+            raise ValueError('linear_rows: group_count needs rows [G, R] and one int32 count per group')
+        grows, gstride = rows.shape[1], (group_count.stride(0) if group_count.dim() else 1)
+    check(_lib.lib().gf_linear_rows(_p(rows), int(row_align), _p(group_count), gstride, grows, k, _p(w), _p(bias), _p(rowgroup_bias), int(rowgroup_rows), int(epilogue),
+                                    _p(g), _p(b), float(eps), _p(res), ldres, _p(row_flag), int(flag_rows), _p(out), N, _dt(w), M, N,
+                                    _stream()), 'gf_linear_rows')
     return out
 
 

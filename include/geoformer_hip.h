@@ -39,13 +39,14 @@ typedef enum { GF_F32 = 0, GF_F16 = 1, GF_BF16 = 2 } gf_dtype;
  * version 3 gives wrong channels) and GF_CONV_PAD16 now states that channels 196 .. 223 are padding; new: GF_CONV_S2, gf_lateral_upsample_add_nhwc. */
 /* Still 4 with gf_pos_encode_ptrs / gf_fine_gather_ptrs and gf_pos_encode_ragged / gf_fine_gather_ragged (with gf_map_record): entries appended at
  * the end change no existing one; a binding that needs them fails at load on the missing symbol (geoformer_amd/_lib.py binds every name).
- * Likewise with the gf_keypoint_* entries and gf_fundamental_*. */
+ * Likewise with the gf_keypoint_* entries, gf_fundamental_*, gf_linear_rows, gf_index_rows and gf_fine_rows*. */
 #define GF_ABI_VERSION 4
 int gf_abi_version(void);
 const char* gf_last_error(void);
 
 /* Optional per-kernel timing with HIP events on the launch stream (used by bench.py's `roofline`).
  * Tags: "k1_stats" (work = flops), "k1_conf" (work = algorithmic bytes), "k3_linear" (work = flops).
+ * gf_linear_rows records under "k3_linear" too (with group_count it declares only the bytes that move whatever the counts are: weights + table).
  * gf_profile_collect synchronises on the recorded events and returns their summed time, count and work. */
 void gf_profile_enable(int on);
 void gf_profile_filter(const char* tag);   /* record only this tag (NULL: all): keeps the event count inside a timed region small */
@@ -703,6 +704,49 @@ size_t gf_fundamental_workspace_bytes(int N, int M, int iters);
 int gf_fundamental_ransac(const float* matches, const float* scores, const int32_t* offsets, int N, int M, float sc_thres,
                           float pixel_thr, int iters, uint32_t seed, double* F, int32_t* valid, int32_t* n_inliers, int32_t* best,
                           uint8_t* inliers, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * K3 with a row-address table as the A operand: a gather fused into the GEMM's operand staging.
+ *   gf_linear_rows   out[m, :] = epi( row(m) . W^T + bias + rowgroup_bias ), row(m) = the k elements at address row_table[m] (DEVICE memory,
+ *            M entries of 64 bits, entries may repeat), or k zeros where row_table[m] == 0.  Everything else as in gf_linear (single-part
+ *            operand): w [N][k], bias, rowgroup_bias / rowgroup_rows, the epilogues, out / ldo.  16-bit types only (fp32:
+ *            GF_ERR_INVALID_ARGUMENT), k a multiple of 64.  row_align: the CALLER'S PROMISE about the table - a power of two, in bytes, that
+ *            divides every non-zero entry, at least 16 (rows are staged as 16-byte pieces).  The entries live in device memory and are
+ *            not inspected: the argument exists so that a caller who cannot make the promise gets GF_ERR_INVALID_ARGUMENT instead of
+ *            misaligned loads; it selects nothing.  Same tile walk, K loop and matrix-instruction order as gf_linear: the output
+ *            bits are those of gf_linear on the rows copied into a buffer.  The table and the rows must stay valid until the launch has run.
+ *            group_count (NULL: off): counts that live on the DEVICE.  The M rows come in groups of group_rows; int32
+ *            group_count[g * group_count_stride] says how many leading rows of group g are wanted.  The other rows are don't-care: a
+ *            128-row tile that holds none of the wanted rows is not computed and its rows of `out` stay UNWRITTEN; don't-care rows of
+ *            other tiles are computed like any row (their table entries must be valid).  No host synchronisation.
+ *   gf_index_rows    the table of a token list: rows[n][j] = x + (n * L + clamp(idx[n * idx_stride + j], 0, L - 1)) * row_bytes for x of N samples
+ *            of L rows (int32 idx with at least L entries per sample; entries behind a sample's count may hold anything).  With
+ *            gf_linear_rows and group_count: the k | v projection of GeoTransformer's self layers at the inlier tokens only.
+ *   gf_fine_rows / gf_fine_rows_ptrs / gf_fine_rows_ragged   the tables of FinePreprocess.forward for gf_linear_rows, instead of the copies of
+ *            gf_fine_gather and its siblings (same map sources, same meaning of every shared argument; 16-bit maps whose channel rows are
+ *            contiguous and 16-byte aligned: sc == 1, sh and sw multiples of 8 elements - checked, for a ragged table the caller's promise):
+ *            win_rows [2M][window^2]: the address of each tap's channel row (image0's windows first), 0 where gf_fine_gather writes zeros (a
+ *            tap outside the map, or outside a ragged map's own extent); coarse_rows [2M]: the addresses of the coarse feature rows
+ *            feat_c0[b][i], feat_c1[b][j] (what gf_fine_gather copies into ccat).  One launch, no host synchronisation.
+ *            feat_align (_ptrs, _ragged): as in the gather's siblings a promise about the table entries, here required to be at least 16
+ *            and otherwise unused - there is one form of the kernel.
+ * ------------------------------------------------------------------------------------------ */
+int gf_linear_rows(const uint64_t* row_table, int row_align, const int32_t* group_count, int group_count_stride, int group_rows, int k,
+                   const void* w, const float* bias, const void* rowgroup_bias, int rowgroup_rows, int epilogue, const float* ln_gamma, const float* ln_beta, float ln_eps, const void* residual,
+                   long ldres, const int32_t* row_flag, int flag_rows, void* out, long ldo, int dtype, int M, int N, void* stream);
+int gf_index_rows(const void* x, long row_bytes, const int32_t* idx, long idx_stride, int N, int L, uint64_t* rows, void* stream);
+int gf_fine_rows(const void* feat_f0, const void* feat_f1, const long* strides0, const long* strides1, int H0, int W0, int H1,
+                 int W1, const void* feat_c0, const void* feat_c1, int L, int S, int CC, const int64_t* b_ids,
+                 const int64_t* i_ids, const int64_t* j_ids, int M, int w0c, int w1c, int stride, int window,
+                 uint64_t* win_rows, uint64_t* coarse_rows, void* stream);
+int gf_fine_rows_ptrs(const void* const* f0_table, const void* const* f1_table, int N, int feat_align, const long* strides0,
+                      const long* strides1, int H0, int W0, int H1, int W1, const void* feat_c0, const void* feat_c1, int L,
+                      int S, int CC, const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids, int M, int w0c, int w1c,
+                      int stride, int window, uint64_t* win_rows, uint64_t* coarse_rows, void* stream);
+int gf_fine_rows_ragged(const gf_map_record* f0_table, const gf_map_record* f1_table, int N, int feat_align, const void* feat_c0,
+                        const void* feat_c1, int L, int S, int CC, const int64_t* b_ids, const int64_t* i_ids,
+                        const int64_t* j_ids, int M, int w0c, int w1c, int stride, int window, uint64_t* win_rows,
+                        uint64_t* coarse_rows, void* stream);
 
 #ifdef __cplusplus
 }

@@ -57,13 +57,16 @@ def family(name):
     return ''.join(out)[:72]
 
 
+# the two backbone instances of K3's linear_kernel<T, NB, EPI, CONVX, AROWS>, by the tail of their template list (one place: a new template
+# argument changes every family name, and a pattern that no longer matches would silently move these kernels under k3_linear)
+K3_UPADD, K3_CONV1X1 = ', 4, 5, true, false>', ', 4, 0, true, false>'
 # bench.py's roofline tags -> the kernel families a tagged call launches (substring match on the family name)
 TAG_FAMILIES = {
     'enc_layer': ['enc_layer<'],
     'enc_kv_state': ['enc_kv_state<', 'enc_kv_reduce'],
-    'k3_linear': ['linear_kernel'],              # minus TAG_EXCLUDE: the EPI_UPADD instance belongs to the backbone
-    'k3_upadd': [', 4, 5, true>'],                # linear_kernel<T, 4, EPI_UPADD = 5, CONVX>
-    'conv1x1': [', 4, 0, true>'],                 # linear_kernel<T, 4, EPI_NONE, CONVX>: gf_conv1x1_nhwc
+    'k3_linear': ['linear_kernel'],              # minus TAG_EXCLUDE: the CONVX instances belong to the backbone; gf_linear_rows' AROWS instances stay
+    'k3_upadd': [K3_UPADD],                       # linear_kernel<T, 4, EPI_UPADD = 5, CONVX, AROWS = false>
+    'conv1x1': [K3_CONV1X1],                      # linear_kernel<T, 4, EPI_NONE, CONVX, AROWS = false>: gf_conv1x1_nhwc
     'k1_stats': ['k1_stats'],
     'k1_conf': ['k1_conf'],
     'k1_unit': ['k1_'],
@@ -74,9 +77,9 @@ TAG_FAMILIES = {
     'bias_act': ['bias_act<'],
     'conv3x3': ['conv3x3_kernel'],
 }
-TAG_EXCLUDE = {'k3_linear': [', 4, 5, true>', ', 4, 0, true>']}
+TAG_EXCLUDE = {'k3_linear': [K3_UPADD, K3_CONV1X1]}
 # the family whose call count equals the number of tagged calls
-TAG_PRIMARY = {'k1_unit': 'k1_compact', 'fine_layer': 'fine_layer<', 'k4_self_attention': ('attn_self_head<', 'attn_self<'), 'enc_layer': 'enc_layer<', 'enc_kv_state': 'enc_kv_state<', 'k3_linear': 'linear_kernel', 'k3_upadd': ', 4, 5, true>', 'conv1x1': ', 4, 0, true>', 'k1_stats': 'k1_stats',
+TAG_PRIMARY = {'k1_unit': 'k1_compact', 'fine_layer': 'fine_layer<', 'k4_self_attention': ('attn_self_head<', 'attn_self<'), 'enc_layer': 'enc_layer<', 'enc_kv_state': 'enc_kv_state<', 'k3_linear': 'linear_kernel', 'k3_upadd': K3_UPADD, 'conv1x1': K3_CONV1X1, 'k1_stats': 'k1_stats',
                'k1_conf': 'k1_conf', 'k2_linear_attention': ('la16_apply', 'la_apply', 'la_small'), 'k5_window_attention': ('window_cross_tiled', 'window_cross_attention'),
                'bias_act': 'bias_act<', 'conv3x3': 'conv3x3_kernel'}
 
