@@ -199,20 +199,40 @@ def linear_attention_fused(q, k, v, st, q_mask=None, kv_mask=None, eps: float = 
     return rt(num * (1.0 / den)[..., None], st)
 
 
-def _finish_fused(P, prefix, x, msg, kind, st, round_out=True):
+def layer_norm_one_pass(x, weight, bias, eps: float):
+    """nn.LayerNorm as K9 and K11 evaluate it (k9_encoder_fused.hip:stats_finish, k11_fine_layer.hip:ln_stats): ONE pass in fp32 - the sum and
+    the sum of squares of the row, mean = s / C, var = max(q - s * mean, 0) / C, rstd = 1 / sqrt(var + eps) - and the normalised value
+    as t * rstd - mean * rstd.  (F.layer_norm centres the row first; the two forms part when |mean| / std of a row is large: q - s * mean
+    cancels.)  fp32 in, fp32 out; the summation ORDER is torch's, not the kernels'."""
+    x = x.float()
+    c = x.shape[-1]
+    one = torch.tensor(1.0, dtype=torch.float32)
+    s = x.sum(-1, keepdim=True)
+    q = (x * x).sum(-1, keepdim=True)
+    mean = s * (one / c)
+    rstd = one / torch.sqrt(torch.clamp(q - s * mean, min=0.) * (one / c) + torch.tensor(eps, dtype=torch.float32))
+    return (x * rstd - mean * rstd) * weight + bias
+
+
+def _ln(x, c, weight, bias, one_pass, eps: float = 1e-5):
+    return layer_norm_one_pass(x, weight, bias, eps) if one_pass else F.layer_norm(x, (c,), weight, bias, eps)
+
+
+def _finish_fused(P, prefix, x, msg, kind, st, round_out=True, one_pass=False):
     """x, msg [N,L,C] (rounded) -> x + LN2(W_2 act(W_1 [x | LN1(W_m msg)])).  round_out=False keeps the fp32 sum (the rounding
-    ablation of tools/rounding_ablation.py: what the features cost the dual-softmax by being STORED in 16 bits)."""
+    ablation of tools/rounding_ablation.py: what the features cost the dual-softmax by being STORED in 16 bits).  one_pass: the two
+    LayerNorms with the kernels' one-pass statistics (layer_norm_one_pass) instead of F.layer_norm's centred ones."""
     c = x.shape[-1]
     W = lambda name: rt(P[prefix + name], st)                                    # noqa: E731
     m = F.linear(msg, W('merge.weight'))
-    m = rt(F.layer_norm(m, (c,), P[prefix + 'norm1.weight'], P[prefix + 'norm1.bias']), st)
+    m = rt(_ln(m, c, P[prefix + 'norm1.weight'], P[prefix + 'norm1.bias'], one_pass), st)
     hid = F.linear(torch.cat([x, m], dim=2), W('mlp.0.weight'))
     hid = rt(torch.relu(hid) if kind == 'loftr' else torch.tanh(hid), st)
-    o = F.layer_norm(F.linear(hid, W('mlp.2.weight')), (c,), P[prefix + 'norm2.weight'], P[prefix + 'norm2.bias'])
+    o = _ln(F.linear(hid, W('mlp.2.weight')), c, P[prefix + 'norm2.weight'], P[prefix + 'norm2.bias'], one_pass)
     return rt(x + o, st) if round_out else x + o
 
 
-def encoder_layer_fused(P, prefix, x, source, nhead, st, x_mask=None, source_mask=None, round_out=True):
+def encoder_layer_fused(P, prefix, x, source, nhead, st, x_mask=None, source_mask=None, round_out=True, one_pass=False):
     """LoFTR (linear attention, ReLU) layer in the 'fused' storage mode; x, source already rounded."""
     n, _, c = x.shape
     d = c // nhead
@@ -221,7 +241,22 @@ def encoder_layer_fused(P, prefix, x, source, nhead, st, x_mask=None, source_mas
     k = F.linear(source, W('k_proj.weight')).view(n, -1, nhead, d)
     v = F.linear(source, W('v_proj.weight')).view(n, -1, nhead, d)
     msg = linear_attention_fused(q, k, v, st, x_mask, source_mask).reshape(n, -1, c)
-    return _finish_fused(P, prefix, x, msg, 'loftr', st, round_out)
+    return _finish_fused(P, prefix, x, msg, 'loftr', st, round_out, one_pass)
+
+
+def encoder_kv_state_fused(P, prefix, source, nhead, st, source_mask=None):
+    """The state gf_encoder_kv_state (and the layer's state tail, gf_encoder_layer_kv) leaves for `source` [N,S,C] (rounded):
+    (KV [N,H,D,D] = sum_s round(phi(k_s))^T round(v_s), Ksum [N,H,D] = sum_s phi(k_s)), both fp32 and NOT yet divided by S; k, v are the
+    un-rounded fp32 projections, phi(k) of a masked row is 0, Ksum adds the un-rounded phi(k).  As the kernels store it, a state row is
+    cat([KV.reshape(N, C * D), Ksum.reshape(N, C)], 1): KV as [c = h * D + d][v]."""
+    n, _, c = source.shape
+    d = c // nhead
+    k = F.linear(source, rt(P[prefix + 'k_proj.weight'], st)).view(n, -1, nhead, d)
+    v = F.linear(source, rt(P[prefix + 'v_proj.weight'], st)).view(n, -1, nhead, d)
+    Kf = _phi(k)
+    if source_mask is not None:
+        Kf = Kf * source_mask[:, :, None, None]
+    return torch.einsum('nshd,nshv->nhdv', rt(Kf, st), rt(v, st)), Kf.sum(dim=1)
 
 
 def linear_attention_window(q, k, v, st, q_mask=None, kv_mask=None, eps: float = 1e-6):
@@ -244,10 +279,11 @@ def linear_attention_window(q, k, v, st, q_mask=None, kv_mask=None, eps: float =
     return rt(num / den[..., None], st)
 
 
-def encoder_layer_chain(P, prefix, x, source, nhead, st, x_mask=None, source_mask=None):
+def encoder_layer_chain(P, prefix, x, source, nhead, st, x_mask=None, source_mask=None, one_pass=False):
     """LoFTR layer in the 'chain' storage mode (K3 linears + K2 attention of short sequences, the fine level).  The
     attention: 8 heads of 16 over <= 32 tokens in a 16-bit mode runs la_window_mfma (linear_attention_window above); any
-    other shape runs la_small, which evaluates phi, the state and the normaliser in fp32 from the stored q, k, v."""
+    other shape runs la_small, which evaluates phi, the state and the normaliser in fp32 from the stored q, k, v.  one_pass: the
+    LayerNorm statistics of K11 (layer_norm_one_pass); the K3 epilogue of the chain itself centres the row first."""
     n, _, c = x.shape
     d = c // nhead
     W = lambda name: rt(P[prefix + name], st)                                    # noqa: E731
@@ -267,9 +303,9 @@ def encoder_layer_chain(P, prefix, x, source, nhead, st, x_mask=None, source_mas
         KV = torch.einsum('nshd,nshv->nhdv', K, v / s_len)
         Z = 1 / (torch.einsum('nlhd,nhd->nlh', Q, K.sum(dim=1)) + 1e-6)
         msg = rt(torch.einsum('nlhd,nhdv,nlh->nlhv', Q, KV, Z) * s_len, st).reshape(n, -1, c)
-    m = rt(F.layer_norm(F.linear(msg, W('merge.weight')), (c,), P[prefix + 'norm1.weight'], P[prefix + 'norm1.bias']), st)
+    m = rt(_ln(F.linear(msg, W('merge.weight')), c, P[prefix + 'norm1.weight'], P[prefix + 'norm1.bias'], one_pass), st)
     hid = rt(torch.relu(F.linear(torch.cat([x, m], dim=2), W('mlp.0.weight'))), st)
-    o = rt(F.layer_norm(F.linear(hid, W('mlp.2.weight')), (c,), P[prefix + 'norm2.weight'], P[prefix + 'norm2.bias']), st)
+    o = rt(_ln(F.linear(hid, W('mlp.2.weight')), c, P[prefix + 'norm2.weight'], P[prefix + 'norm2.bias'], one_pass), st)
     return rt(x + o, st)
 
 
