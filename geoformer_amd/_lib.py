@@ -151,6 +151,9 @@ SIGNATURES = {
     'gf_fundamental_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'gf_fundamental_ransac': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_int, c_uint32, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'gf_fundamental_lo_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'gf_fundamental_ransac_lo': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_int, c_uint32, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     'gf_linear_rows': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p,
                                c_long, c_void_p, c_int, c_void_p, c_long, c_int, c_int, c_int, c_void_p]),
     'gf_index_rows': (c_int, [c_void_p, c_long, c_void_p, c_long, c_int, c_int, c_void_p, c_void_p]),

@@ -23,10 +23,33 @@
 //                   both boxes have an extent and some hypothesis produced a solution.  The mask is the winner's inlier set over the pair's
 //                   ORIGINAL rows; filtered rows are 0.
 //
-// NOT part of this: no refit on the inliers, no local optimisation, no planar-degeneracy test (matches on one plane give a valid but
-// arbitrary F), no adaptive stop.  OpenCV parity (cv2.findFundamentalMat) is UNPINNED; what is pinned is the algorithm written here.
+//   refit           (gf_fundamental_ransac_lo with refit_rounds R in 1 .. FS_REFIT_MAX_ROUNDS only; R = 0 is everything above and nothing
+//                   else.)  The winner is ONE seven-point model; a least-squares fit on its consensus set follows, up to R times.
+//                   cur = (F, inlier set over the surviving rows, count) starts as the winner's.  One round:
+//                   1. cur has fewer than FS_REFIT_MIN_INLIERS (8) inliers: stop.
+//                   2. fs_refit_row: a = x1 (x) x0 of a surviving row in box-normalised coordinates, the row fs_seven_point builds.
+//                      fs_refit_accum adds the 45 distinct entries of a a^T (entry (i, j), i <= j, at fs_sym_index) to an accumulator.
+//                      M = sum over the inliers, in THIS order: partial j (0 .. FS_REFIT_PARTIALS - 1 = 255) starts from +0.0 and adds
+//                      the inlier rows with compacted index i = j (mod 256), ascending i; the partials are combined inside each block of
+//                      64 with strides 32, 16, 8, 4, 2, 1 (s[j] = s[j] + s[j + stride], j < stride within the block) and the four block
+//                      sums as (b0 + b1) + (b2 + b3): fs_refit_tree.  (A wave's xor butterfly gives lane 0 these bits: the addition of
+//                      two fp64 numbers is commutative.)
+//                   3. fs_refit_solve: the eigenvector of M's smallest eigenvalue by gs_jacobi_sym<9>, FS_JACOBI9_SWEEPS sweeps.
+//                   4. rank 2 without an SVD: v = the eigenvector of F^T F's smallest eigenvalue (gs_jacobi_sym<3>, FS_JACOBI3_SWEEPS),
+//                      F <- F - (F v) v^T, the Frobenius-closest rank-2 matrix.  Then Frobenius norm 1, T1^T F T0, norm 1 again, as
+//                      the seven-point solutions.
+//                   5. a non-finite entry or a zero norm: the round fails; cur stays, stop.
+//                   6. the candidate is scored over ALL surviving rows with fs_inlier and the same thr^2; it is accepted iff its count
+//                      is >= cur's.  Accepted: cur <- candidate, rounds += 1.  Stop when it was rejected, or when the accepted set equals
+//                      the one before (a fixed point).
+//                   So n_inliers never decreases; rounds = 0 means every output is the seven-point winner's, bit for bit; `best` keeps
+//                   naming the (hypothesis, root) that seeded the result.  A planar or otherwise degenerate consensus set gives SOME
+//                   eigenvector of a rank-deficient M and the accept test alone decides.
 //
-// Workspace: FS_WS_DOUBLES doubles through GsWs.
+// NOT part of this: no Sampson re-weighting (IRLS) or other local optimisation, no planar-degeneracy test (matches on one plane give a
+// valid but arbitrary F), no adaptive stop.  OpenCV parity (cv2.findFundamentalMat) is UNPINNED; what is pinned is the algorithm written here.
+//
+// Workspace: FS_WS_DOUBLES doubles through GsWs for the seven-point solver, FS_REFIT_WS_DOUBLES for fs_refit_solve.
 #pragma once
 #include "keypoint_spec.h"
 #include "solver_common.h"
@@ -192,4 +215,128 @@ GS_HD int fs_seven_point(const double (&x0)[7][2], const double (&x1)[7][2], con
 // inlier iff the squared Sampson distance of the pixel match under F is below thr^2
 GS_HD int fs_inlier(const double (&F)[9], const float* m4, double thr2) {
     return gs_sampson(F, (double)m4[0], (double)m4[1], (double)m4[2], (double)m4[3]) < thr2;      // a NaN is never an inlier
+}
+
+// ------------------------------------------------------------------------------------------------------------ refit on the inliers
+#define FS_REFIT_MAX_ROUNDS 8
+#define FS_REFIT_MIN_INLIERS 8
+#define FS_REFIT_PARTIALS 256     /* partial sums of the normal matrix: the threads of one workgroup */
+#define FS_JACOBI9_SWEEPS 10
+#define FS_JACOBI3_SWEEPS 8
+#define FS_SYM9 45                /* distinct entries of a symmetric 9 x 9 matrix */
+
+// workspace of fs_refit_solve (doubles, stride as the caller likes)
+#define FS_REFIT_OFF_ACC 0        /* [45] the normal matrix, entry (i, j), i <= j, at fs_sym_index(i, j) */
+#define FS_REFIT_OFF_A 45         /* [9][9] the same, both triangles; its eigenvalues on the diagonal afterwards */
+#define FS_REFIT_OFF_V 126        /* [9][9] eigenvectors in the columns */
+#define FS_REFIT_OFF_G 207        /* [3][3] F^T F */
+#define FS_REFIT_OFF_W 216        /* [3][3] its eigenvectors */
+#define FS_REFIT_WS_DOUBLES 225
+
+GS_HD constexpr int fs_sym_index(int i, int j) { return 9 * i - (i * (i - 1)) / 2 + (j - i); }      // i <= j
+
+// a = x1 (x) x0 in box-normalised coordinates: the row of the epipolar system, with the expressions of fs_seven_point
+GS_HD void fs_refit_row(const float* m4, const double (&nm)[6], double (&r)[9]) {
+    const double a = ((double)m4[0] - nm[0]) / nm[2], b = ((double)m4[1] - nm[1]) / nm[2];
+    const double u = ((double)m4[2] - nm[3]) / nm[5], v = ((double)m4[3] - nm[4]) / nm[5];
+    r[0] = u * a; r[1] = u * b; r[2] = u;
+    r[3] = v * a; r[4] = v * b; r[5] = v;
+    r[6] = a; r[7] = b; r[8] = 1.0;
+}
+
+GS_HD void fs_refit_accum(double (&acc)[FS_SYM9], const double (&r)[9]) {
+    GS_UNROLL
+    for (int i = 0; i < 9; ++i) {
+        GS_UNROLL
+        for (int j = i; j < 9; ++j) acc[fs_sym_index(i, j)] = acc[fs_sym_index(i, j)] + r[i] * r[j];
+    }
+}
+
+// the order in which the FS_REFIT_PARTIALS partial sums of one entry become the entry: s [256] is overwritten, the sum is returned
+GS_HD double fs_refit_tree(double* s) {
+    for (int b = 0; b < FS_REFIT_PARTIALS; b += 64)
+        for (int stride = 32; stride >= 1; stride >>= 1)
+            for (int j = 0; j < stride; ++j) s[b + j] = s[b + j] + s[b + j + stride];
+    return (s[0] + s[64]) + (s[128] + s[192]);
+}
+
+// G = T1^T F T0 scaled to Frobenius norm 1: a matrix of normalised coordinates taken back to pixels, with the expressions of
+// fs_seven_point (which keeps its own copy: its kernel is left as it compiled before the refit existed).  Returns 0 for a zero or
+// non-finite norm.
+GS_HD int fs_to_pixels(const double (&F)[9], const double (&nm)[6], double (&out)[9]) {
+    const double i0 = 1.0 / nm[2], i1 = 1.0 / nm[5];
+    const double t0x = -(nm[0] * i0), t0y = -(nm[1] * i0), t1x = -(nm[3] * i1), t1y = -(nm[4] * i1);
+    double H[9], G[9], n2 = 0.0;
+    GS_UNROLL
+    for (int i = 0; i < 3; ++i) {
+        H[3 * i + 0] = F[3 * i + 0] * i0;
+        H[3 * i + 1] = F[3 * i + 1] * i0;
+        H[3 * i + 2] = (F[3 * i + 0] * t0x + F[3 * i + 1] * t0y) + F[3 * i + 2];
+    }
+    GS_UNROLL
+    for (int c = 0; c < 3; ++c) {
+        G[c] = H[c] * i1;
+        G[3 + c] = H[3 + c] * i1;
+        G[6 + c] = (H[c] * t1x + H[3 + c] * t1y) + H[6 + c];
+    }
+    GS_UNROLL
+    for (int k = 0; k < 9; ++k) n2 = n2 + G[k] * G[k];
+    const double nn = sqrt(n2);
+    if (!(nn > 0.0) || !(nn < (double)INFINITY)) return 0;
+    GS_UNROLL
+    for (int k = 0; k < 9; ++k) out[k] = G[k] / nn;
+    return 1;
+}
+
+// Steps 3 - 5 of a round are fs_refit_solve (below): the normal matrix at FS_REFIT_OFF_ACC -> the candidate in PIXEL coordinates,
+// Frobenius norm 1, rank 2; 0 when the round fails (out is then unspecified).  It is written in three parts so that k_fundamental.hip can
+// run the middle one - gs_jacobi_sym<9> - with the elements of a rotation on several lanes, which gives the same bits.
+GS_HD void fs_refit_fill(const GsWs& w) {
+    for (int i = 0; i < 9; ++i)
+        for (int j = i; j < 9; ++j) {
+            const double v = w(FS_REFIT_OFF_ACC + fs_sym_index(i, j));
+            w(FS_REFIT_OFF_A + 9 * i + j) = v;
+            w(FS_REFIT_OFF_A + 9 * j + i) = v;
+        }
+}
+
+GS_HD int fs_refit_finish(const GsWs& w, const double (&nm)[6], double (&out)[9]) {
+    const int col = gs_min_diag<9>(w, FS_REFIT_OFF_A);
+    double F[9];
+    GS_UNROLL
+    for (int k = 0; k < 9; ++k) F[k] = w(FS_REFIT_OFF_V + 9 * k + col);
+    // rank 2: the right singular vector of the smallest singular value is the eigenvector of F^T F's smallest eigenvalue
+    GS_UNROLL
+    for (int i = 0; i < 3; ++i) {
+        GS_UNROLL
+        for (int j = 0; j < 3; ++j) w(FS_REFIT_OFF_G + 3 * i + j) = (F[i] * F[j] + F[3 + i] * F[3 + j]) + F[6 + i] * F[6 + j];
+    }
+    gs_jacobi_sym<3>(w, FS_REFIT_OFF_G, FS_REFIT_OFF_W, FS_JACOBI3_SWEEPS);
+    const int c3 = gs_min_diag<3>(w, FS_REFIT_OFF_G);
+    const double v0 = w(FS_REFIT_OFF_W + c3), v1 = w(FS_REFIT_OFF_W + 3 + c3), v2 = w(FS_REFIT_OFF_W + 6 + c3);
+    double n2 = 0.0;
+    GS_UNROLL
+    for (int i = 0; i < 3; ++i) {
+        const double fv = (F[3 * i] * v0 + F[3 * i + 1] * v1) + F[3 * i + 2] * v2;
+        F[3 * i] = F[3 * i] - fv * v0;
+        F[3 * i + 1] = F[3 * i + 1] - fv * v1;
+        F[3 * i + 2] = F[3 * i + 2] - fv * v2;
+    }
+    GS_UNROLL
+    for (int k = 0; k < 9; ++k) n2 = n2 + F[k] * F[k];
+    const double nn = sqrt(n2);
+    if (!(nn > 0.0) || !(nn < (double)INFINITY)) return 0;
+    GS_UNROLL
+    for (int k = 0; k < 9; ++k) F[k] = F[k] / nn;
+    if (!fs_to_pixels(F, nm, out)) return 0;
+    int finite = 1;
+    GS_UNROLL
+    for (int k = 0; k < 9; ++k) finite &= (out[k] - out[k] == 0.0);
+    return finite;
+}
+
+GS_HD int fs_refit_solve(const GsWs& w, const double (&nm)[6], double (&out)[9]) {
+    fs_refit_fill(w);
+    gs_jacobi_sym<9>(w, FS_REFIT_OFF_A, FS_REFIT_OFF_V, FS_JACOBI9_SWEEPS);
+    return fs_refit_finish(w, nm, out);
 }

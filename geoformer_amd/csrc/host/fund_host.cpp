@@ -33,12 +33,38 @@ int gf_fund_host_pencil(const double* F1, const double* F2, double* F_out) {
     return n;
 }
 
-// One pair: matches [n][4] fp32 pixels, scores [n] or NULL.  Outputs as gf_fundamental_ransac writes them for pair `sample` of a launch:
-// F [9], hyp [2] (hypothesis, root; -1 when not valid), n_inliers [1], mask [n].  Returns valid (0 / 1), or -1 (GF_ERR_INVALID_ARGUMENT)
-// for arguments the device entry point rejects.
-int gf_fund_host_ransac(const float* matches, const float* scores, int n, float sc_thres, double pixel_thr, int iters, uint32_t seed,
-                        uint32_t sample, double* F_out, int32_t* hyp_out, int32_t* n_inliers, uint8_t* mask) {
+// One refit (steps 2 - 5 of a round of fund_solver.h) from a given inlier set: matches [n][4], every row taken as a surviving row,
+// mask [n], norm [6] -> F_out [9] in pixels.  Returns 1, or 0 when the round fails.
+int gf_fund_host_refit_once(const float* matches, int n, const uint8_t* mask, const double* norm, double* F_out) {
+    double nm[6], ws[FS_REFIT_WS_DOUBLES], F[9];
+    for (int i = 0; i < 6; ++i) nm[i] = norm[i];
+    std::vector<double> part((size_t)FS_SYM9 * FS_REFIT_PARTIALS, 0.0);
+    for (int j = 0; j < FS_REFIT_PARTIALS; ++j) {
+        double acc[FS_SYM9], r[9];
+        for (int e = 0; e < FS_SYM9; ++e) acc[e] = 0.0;
+        for (int i = j; i < n; i += FS_REFIT_PARTIALS) {
+            if (!mask[i]) continue;
+            fs_refit_row(matches + 4 * (size_t)i, nm, r);
+            fs_refit_accum(acc, r);
+        }
+        for (int e = 0; e < FS_SYM9; ++e) part[(size_t)e * FS_REFIT_PARTIALS + j] = acc[e];
+    }
+    for (int e = 0; e < FS_SYM9; ++e) ws[FS_REFIT_OFF_ACC + e] = fs_refit_tree(part.data() + (size_t)e * FS_REFIT_PARTIALS);
+    const GsWs w{ws, 1};
+    if (!fs_refit_solve(w, nm, F)) return 0;
+    for (int k = 0; k < 9; ++k) F_out[k] = F[k];
+    return 1;
+}
+
+// One pair: matches [n][4] fp32 pixels, scores [n] or NULL.  Outputs as gf_fundamental_ransac_lo writes them for pair `sample` of a launch:
+// F [9], hyp [2] (hypothesis, root; -1 when not valid), n_inliers [1], mask [n], rounds [1] (the accepted refits; may be NULL when
+// refit_rounds is 0).  Returns valid (0 / 1), or -1 (GF_ERR_INVALID_ARGUMENT) for arguments the device entry point rejects.
+int gf_fund_host_ransac_lo(const float* matches, const float* scores, int n, float sc_thres, double pixel_thr, int iters, uint32_t seed,
+                           uint32_t sample, int refit_rounds, double* F_out, int32_t* hyp_out, int32_t* n_inliers, uint8_t* mask,
+                           int32_t* rounds) {
     if (iters <= 0 || iters % FS_HYP_PER_WG != 0 || n < 0 || !(pixel_thr > 0.0)) return -1;
+    if (refit_rounds < 0 || refit_rounds > FS_REFIT_MAX_ROUNDS || (refit_rounds > 0 && !rounds)) return -1;
+    if (rounds) *rounds = 0;
     for (int k = 0; k < 9; ++k) F_out[k] = 0.0;
     hyp_out[0] = hyp_out[1] = -1;
     *n_inliers = 0;
@@ -91,10 +117,43 @@ int gf_fund_host_ransac(const float* matches, const float* scores, int n, float 
         mask[rows[i]] = (uint8_t)in;
         nin += in;
     }
+    // ---- refit on the inliers: cur = (best, set, nin) over the surviving rows
+    if (refit_rounds > 0) {
+        std::vector<float> sm(4 * (size_t)cnt);               // the surviving rows, compacted
+        std::vector<uint8_t> set(cnt), cand(cnt);
+        for (int i = 0; i < cnt; ++i) {
+            for (int k = 0; k < 4; ++k) sm[4 * (size_t)i + k] = matches[4 * (size_t)rows[i] + k];
+            set[i] = mask[rows[i]];
+        }
+        for (int r = 0; r < refit_rounds; ++r) {
+            if (nin < FS_REFIT_MIN_INLIERS) break;
+            double F[9];
+            if (!gf_fund_host_refit_once(sm.data(), cnt, set.data(), nm, F)) break;
+            int c = 0, differ = 0;
+            for (int i = 0; i < cnt; ++i) {
+                cand[i] = (uint8_t)fs_inlier(F, sm.data() + 4 * (size_t)i, thr2);
+                c += cand[i];
+                differ |= cand[i] != set[i];
+            }
+            if (c < nin) break;
+            for (int k = 0; k < 9; ++k) best[k] = F[k];
+            nin = c;
+            set.swap(cand);
+            ++*rounds;
+            if (!differ) break;
+        }
+        for (int i = 0; i < cnt; ++i) mask[rows[i]] = set[i];
+    }
     for (int k = 0; k < 9; ++k) F_out[k] = best[k];
     hyp_out[0] = best_t; hyp_out[1] = best_r;
     *n_inliers = nin;
     return 1;
+}
+
+// gf_fundamental_ransac: no refit
+int gf_fund_host_ransac(const float* matches, const float* scores, int n, float sc_thres, double pixel_thr, int iters, uint32_t seed,
+                        uint32_t sample, double* F_out, int32_t* hyp_out, int32_t* n_inliers, uint8_t* mask) {
+    return gf_fund_host_ransac_lo(matches, scores, n, sc_thres, pixel_thr, iters, seed, sample, 0, F_out, hyp_out, n_inliers, mask, nullptr);
 }
 
 }   // extern "C"

@@ -12,6 +12,9 @@ extern "C" int gf_fund_host_seven_point(const double* x0, const double* x1, cons
 extern "C" int gf_fund_host_pencil(const double* F1, const double* F2, double* F_out);
 extern "C" int gf_fund_host_ransac(const float* matches, const float* scores, int n, float sc_thres, double pixel_thr, int iters, uint32_t seed,
                                    uint32_t sample, double* F_out, int32_t* hyp_out, int32_t* n_inliers, uint8_t* mask);
+extern "C" int gf_fund_host_ransac_lo(const float* matches, const float* scores, int n, float sc_thres, double pixel_thr, int iters, uint32_t seed,
+                                      uint32_t sample, int refit_rounds, double* F_out, int32_t* hyp_out, int32_t* n_inliers, uint8_t* mask,
+                                      int32_t* rounds);
 
 static uint64_t g_state;
 static double uni() {                                  // [0, 1)
@@ -178,6 +181,47 @@ int main() {
             CHECK(gf_fund_host_ransac(m.data(), nullptr, n, 0.25f, 1.0, 100, 3, 0, F, hyp, &nin, mask.data()) == -1, "iters 100");
             CHECK(gf_fund_host_ransac(m.data(), nullptr, n, 0.25f, 1.0, 0, 3, 0, F, hyp, &nin, mask.data()) == -1, "iters 0");
         }
+    }
+    // ---- the refit on the inliers: noisy scenes (sigma 0.5 px) at the edges of the eight-inlier minimum and of the 256 partial sums
+    for (int n : {7, 8, 9, 257, 600}) {
+        g_state = 500 + n;
+        const Geo p = random_geo();
+        std::vector<float> m(4 * n);
+        for (int i = 0; i < n; ++i) {
+            double a[2], b[2];
+            project(p, a, b);
+            if (n >= 257 && uni() < 0.3) { b[0] = uni() * 640; b[1] = uni() * 480; }
+            m[4 * i] = (float)(a[0] + 0.5 * gauss()); m[4 * i + 1] = (float)(a[1] + 0.5 * gauss());
+            m[4 * i + 2] = (float)(b[0] + 0.5 * gauss()); m[4 * i + 3] = (float)(b[1] + 0.5 * gauss());
+        }
+        double F0[9];
+        int32_t hyp0[2], nin0 = 0;
+        std::vector<uint8_t> mask0(n);
+        for (int R : {0, 1, 8}) {
+            double F[9];
+            int32_t hyp[2], nin = 0, rounds = -1;
+            std::vector<uint8_t> mask(n);
+            const int rc = gf_fund_host_ransac_lo(m.data(), nullptr, n, 0.25f, 1.0, 64, 11, 0, R, F, hyp, &nin, mask.data(), &rounds);
+            int cnt = 0, finite = 1, same = 1;
+            for (int i = 0; i < n; ++i) cnt += mask[i];
+            for (int k = 0; k < 9; ++k) finite &= isfinite(F[k]) != 0;
+            if (R == 0) {
+                for (int k = 0; k < 9; ++k) F0[k] = F[k];
+                hyp0[0] = hyp[0]; hyp0[1] = hyp[1]; nin0 = nin; mask0 = mask;
+            }
+            for (int k = 0; k < 9; ++k) same &= F[k] == F0[k];
+            for (int i = 0; i < n; ++i) same &= mask[i] == mask0[i];
+            CHECK(rc == 1 && finite && cnt == nin && nin >= nin0 && rounds >= 0 && rounds <= R && hyp[0] == hyp0[0] && hyp[1] == hyp0[1],
+                  "refit %d rows R %d: rc %d finite %d mask %d inliers %d (seven-point %d) rounds %d", n, R, rc, finite, cnt, nin, nin0, rounds);
+            CHECK(rounds > 0 || (same && nin == nin0), "refit %d rows R %d: rounds 0 but not the seven-point winner", n, R);
+            CHECK(n != 7 || rounds == 0, "refit of seven inliers: rounds %d", rounds);
+            printf("refit %3d rows R %d: %d -> %d inliers in %d round(s)\n", n, R, nin0, nin, rounds);
+        }
+        double F[9];
+        int32_t hyp[2], nin, rounds;
+        std::vector<uint8_t> mask(n);
+        CHECK(gf_fund_host_ransac_lo(m.data(), nullptr, n, 0.25f, 1.0, 64, 11, 0, 9, F, hyp, &nin, mask.data(), &rounds) == -1, "refit_rounds 9");
+        CHECK(gf_fund_host_ransac_lo(m.data(), nullptr, n, 0.25f, 1.0, 64, 11, 0, -1, F, hyp, &nin, mask.data(), &rounds) == -1, "refit_rounds -1");
     }
     printf(g_fail ? "%d check(s) FAILED\n" : "all checks passed\n", g_fail);
     return g_fail ? 1 : 0;

@@ -13,6 +13,10 @@
 //                      drawn again through the attempt counter, GS_DRAW_ATTEMPTS times at most.
 //   gs_sampson         the squared Sampson distance of a match under a 3x3 matrix: (x1^T S x0)^2 / (Sx0[0]^2 + Sx0[1]^2 + S^Tx1[0]^2 +
 //                      S^Tx1[1]^2), OpenCV's residual for E and F alike.
+//   gs_jacobi_sym<N>   all eigenvectors of a symmetric N x N matrix by cyclic Jacobi: a FIXED number of sweeps, rotations in lexicographic
+//                      (p, q) order, a rotation whose off-diagonal entry is exactly 0 skipped, t = sign(theta) / (|theta| + sqrt(theta^2 + 1)).
+//                      No convergence test: nothing that could differ between two builds decides how much work is done.
+//   gs_min_diag<N>     the index of the smallest diagonal entry (the smallest eigenvalue after gs_jacobi_sym); ties go to the lower index.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -184,4 +188,50 @@ GS_HD double gs_sampson(const double (&S)[9], double x0, double y0, double x1, d
     const double b0 = (S[0] * x1 + S[3] * y1) + S[6], b1 = (S[1] * x1 + S[4] * y1) + S[7];
     const double num = (x1 * a0 + y1 * a1) + a2;
     return (num * num) / (((a0 * a0 + a1 * a1) + b0 * b0) + b1 * b1);
+}
+
+// A [N][N] symmetric at w(off_a + N i + j), BOTH triangles filled and both kept up to date; V [N][N] at w(off_v + N i + j) is set to the
+// identity and leaves with the eigenvectors in its COLUMNS, the eigenvalues on A's diagonal.  Every element of a rotation is independent
+// arithmetic given (c, s, t), so the elements may be spread over lanes without changing a bit.
+template <int N>
+GS_HD void gs_jacobi_sym(const GsWs& w, int off_a, int off_v, int sweeps) {
+    for (int i = 0; i < N; ++i)
+        for (int j = 0; j < N; ++j) w(off_v + N * i + j) = i == j ? 1.0 : 0.0;
+    for (int sw = 0; sw < sweeps; ++sw)
+        for (int p = 0; p < N - 1; ++p)
+            for (int q = p + 1; q < N; ++q) {
+                const double apq = w(off_a + N * p + q);
+                if (apq == 0.0) continue;
+                const double app = w(off_a + N * p + p), aqq = w(off_a + N * q + q);
+                const double theta = (aqq - app) / (2.0 * apq);
+                const double mag = 1.0 / (fabs(theta) + sqrt(theta * theta + 1.0));
+                const double t = theta < 0.0 ? -mag : mag;
+                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+                w(off_a + N * p + p) = app - t * apq;
+                w(off_a + N * q + q) = aqq + t * apq;
+                w(off_a + N * p + q) = 0.0;
+                w(off_a + N * q + p) = 0.0;
+                for (int k = 0; k < N; ++k) {
+                    if (k != p && k != q) {
+                        const double akp = w(off_a + N * k + p), akq = w(off_a + N * k + q);
+                        const double np = c * akp - s * akq, nq = s * akp + c * akq;
+                        w(off_a + N * k + p) = np; w(off_a + N * p + k) = np;
+                        w(off_a + N * k + q) = nq; w(off_a + N * q + k) = nq;
+                    }
+                    const double vkp = w(off_v + N * k + p), vkq = w(off_v + N * k + q);
+                    w(off_v + N * k + p) = c * vkp - s * vkq;
+                    w(off_v + N * k + q) = s * vkp + c * vkq;
+                }
+            }
+}
+
+template <int N>
+GS_HD int gs_min_diag(const GsWs& w, int off_a) {
+    int best = 0;
+    double lo = w(off_a);
+    for (int i = 1; i < N; ++i) {
+        const double d = w(off_a + N * i + i);
+        if (d < lo) { lo = d; best = i; }
+    }
+    return best;
 }

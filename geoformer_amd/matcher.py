@@ -524,15 +524,19 @@ class VerifiedMatches(NamedTuple):
     n_inliers: np.ndarray    # [P] int32
     verified: np.ndarray     # [P] bool: a model was found and it has at least min_inliers inliers
     masks: list              # per pair: [n_p] bool, the inliers of a verified pair; all False otherwise
+    rounds: np.ndarray       # [P] int32: refits on the inliers accepted per pair (zeros without refit)
 
 
-def verify_matches(pairs, results, thr=1.0, min_inliers=15, sc_thres=0.25, iters=None, device='cuda'):
+def verify_matches(pairs, results, thr=1.0, min_inliers=15, sc_thres=0.25, iters=None, device='cuda', refit=0):
     """Geometric verification of the matches of every pair, for image sets without poses or intrinsics: a detector-free matcher returns
     confident-looking matches for pairs that show different scenes, and a track should only see matches that one epipolar geometry
     explains.  Per pair a fundamental-matrix RANSAC (ops.ransac_fundamental: rows scoring below sc_thres or not finite take no part,
     seven-point hypotheses, squared Sampson distance below thr^2 pixels; the rule is csrc/fund_solver.h) - one upload, three launches for
-    all pairs, one read back.  verified[p] = a model was found and n_inliers[p] >= min_inliers.  No refit and no planar-degeneracy test:
-    the F of a planar scene is valid but arbitrary, its inlier set is still the plane's.  pairs / results as consolidate_matches takes them."""
+    all pairs, one read back.  verified[p] = a model was found and n_inliers[p] >= min_inliers.  refit = R in 1 .. 8: one more launch
+    refits every winner on its inliers up to R times (normalised eight-point fit, rank 2, inliers selected again; never fewer inliers
+    than before); F, n_inliers, verified and masks are then the refined model's and rounds counts the accepted refits.  No
+    planar-degeneracy test: the F of a planar scene is valid but arbitrary, its inlier set is still the plane's.  pairs / results as
+    consolidate_matches takes them."""
     if len(pairs) != len(results):
         raise ValueError(f'verify_matches: {len(pairs)} pairs but {len(results)} results')
     P = len(results)
@@ -541,22 +545,25 @@ def verify_matches(pairs, results, thr=1.0, min_inliers=15, sc_thres=0.25, iters
     if any(len(m) != len(x) for m, x in zip(ms, ss)):
         raise ValueError('verify_matches: a result whose matches and scores differ in length')
     if P == 0:
-        return VerifiedMatches(np.zeros((0, 3, 3)), np.zeros(0, np.int32), np.zeros(0, bool), [])
+        return VerifiedMatches(np.zeros((0, 3, 3)), np.zeros(0, np.int32), np.zeros(0, bool), [], np.zeros(0, np.int32))
     offsets = np.concatenate([[0], np.cumsum([len(m) for m in ms])]).astype(np.int32)
     M = int(offsets[-1])
     block = np.concatenate([a.reshape(-1).view(np.int32) for a in (*ms, *ss, offsets)])
     with torch.cuda.device(device):
         d = torch.from_numpy(block).to(device)
         rs = ops.ransac_fundamental(d[:4 * M].view(torch.float32).view(M, 4), d[4 * M:5 * M].view(torch.float32), d[5 * M:], P, pixel_thr=thr,
-                                    sc_thres=sc_thres, iters=ops.FUND_RANSAC_ITERS if iters is None else iters)
-        out = torch.cat([rs[k].reshape(-1).view(torch.uint8) for k in ('F', 'valid', 'n_inliers', 'inliers')]).cpu().numpy()
+                                    sc_thres=sc_thres, iters=ops.FUND_RANSAC_ITERS if iters is None else iters, refit=refit)
+        if not refit:
+            rs['rounds'] = torch.zeros(P, dtype=torch.int32, device=rs['valid'].device)
+        out = torch.cat([rs[k].reshape(-1).view(torch.uint8) for k in ('F', 'valid', 'n_inliers', 'rounds', 'inliers')]).cpu().numpy()
     F = out[:72 * P].view(np.float64).reshape(P, 3, 3).copy()
     valid = out[72 * P:76 * P].view(np.int32)
     nin = out[76 * P:80 * P].view(np.int32).copy()
-    inl = out[80 * P:].astype(bool)
+    rounds = out[80 * P:84 * P].view(np.int32).copy()
+    inl = out[84 * P:].astype(bool)
     verified = (valid == 1) & (nin >= min_inliers)
     masks = [inl[offsets[p]:offsets[p + 1]].copy() if verified[p] else np.zeros(len(ms[p]), bool) for p in range(P)]
-    return VerifiedMatches(F, nin, verified, masks)
+    return VerifiedMatches(F, nin, verified, masks, rounds)
 
 
 def write_consolidated(out_dir, cm: ConsolidatedMatches):
@@ -626,14 +633,14 @@ def estimate_relative_pose(matches, K0, K1, thr=0.5, device='cuda'):
     return rs['R'][0].cpu().numpy(), rs['t'][0].cpu().numpy(), rs['inliers'].cpu().numpy().astype(bool)
 
 
-def estimate_fundamental(matches, thr=1.0, device='cuda'):
+def estimate_fundamental(matches, thr=1.0, device='cuda', refit=0):
     """Fundamental-matrix RANSAC from [n,4] pixel matches on the device (no intrinsics needed; csrc/fund_solver.h); returns
-    (F with x1^T F x0 = 0 and Frobenius norm 1, inlier mask) or None."""
+    (F with x1^T F x0 = 0 and Frobenius norm 1, inlier mask) or None.  refit: up to that many refits of the winner on its inliers (0 .. 8)."""
     if len(matches) < 7:
         return None
     m = torch.as_tensor(np.asarray(matches), dtype=torch.float32, device=device)
     offsets = torch.tensor([0, len(m)], dtype=torch.int32, device=device)
-    rs = ops.ransac_fundamental(m[:, :4].contiguous(), None, offsets, 1, pixel_thr=thr)
+    rs = ops.ransac_fundamental(m[:, :4].contiguous(), None, offsets, 1, pixel_thr=thr, refit=refit)
     if int(rs['valid'][0]) == 0:
         return None
     return rs['F'][0].cpu().numpy(), rs['inliers'].cpu().numpy().astype(bool)
@@ -713,7 +720,7 @@ def eval_hpatches(matcher, data_root, ransac_thres=3, thres=(1, 3, 5, 10), scale
 #   python -m geoformer_amd.matcher hpatches /path/to/hpatches-sequences-release [--ckpt ...] [--preprocess device] [--reuse-features]
 #   python -m geoformer_amd.matcher pairs LIST | --all-pairs DIR  [--out DIR] [--batch B] [--cache-gb G] [--pad [--pad-waste R]]   (no reference counterpart)
 #                                         [--keypoints DIR [--sc-thres S] [--qt-psize P] [--qt-dthres D] [--no-qt-unique]]   (process_matches_and_keypoints_exporth5)
-#                                         [--verify [--verify-thr T] [--min-inliers K]]   (two-view verification: fundamental-matrix RANSAC per pair)
+#                                         [--verify [--verify-thr T] [--min-inliers K] [--verify-refit [R]]]   (two-view verification: fundamental-matrix RANSAC per pair)
 # ---------------------------------------------------------------------------------------------
 def build_parser():
     """Defaults follow the reference per sub-command: `match` = inference.py:107 (imsize 640, matches scaled back to the
@@ -762,6 +769,9 @@ def build_parser():
                         'F, inliers and verified; with --keypoints only the inliers of verified pairs are consolidated and two_view.npz is written')
     q.add_argument('--verify-thr', type=float, default=1.0, help='with --verify: inlier threshold, Sampson distance in pixels')
     q.add_argument('--min-inliers', type=int, default=15, help='with --verify: a pair with fewer inliers is not verified')
+    q.add_argument('--verify-refit', type=int, nargs='?', const=4, default=0, metavar='R',
+                   help='with --verify: refit every pair\'s model on its inliers up to R times (1 .. 8; the bare flag: 4) and select the inliers '
+                        'again; each .npz of --out and two_view.npz gain refit_rounds')
     for p in (h, q):
         p.add_argument('--cache-gb', type=float, default=None,
                        help='byte budget of the feature store in GB: least recently used images are dropped and extracted again when '
@@ -799,23 +809,26 @@ def main(argv=None):
     if args.cmd == 'pairs':
         pairs = read_pair_list(args.list) if args.list is not None else all_pairs(args.all_pairs)
         results = matcher.match_many(pairs, batch=args.batch, pad=args.pad, max_waste=args.pad_waste)
-        vm = verify_matches(pairs, results, args.verify_thr, args.min_inliers, args.sc_thres, device=matcher.device) if args.verify else None
+        vm = (verify_matches(pairs, results, args.verify_thr, args.min_inliers, args.sc_thres, device=matcher.device, refit=args.verify_refit)
+              if args.verify else None)
+        refit = {} if vm is None or not args.verify_refit else {'refit_rounds': vm.rounds}
         if args.out:
             os.makedirs(args.out, exist_ok=True)
         for k, ((p0, p1), res) in enumerate(zip(pairs, results)):
             if args.out:
                 stem = '_'.join(os.path.splitext(os.path.basename(p))[0] for p in (p0, p1))
-                extra = {} if vm is None else {'F': vm.F[k], 'inliers': vm.masks[k], 'verified': vm.verified[k]}
+                extra = {} if vm is None else {'F': vm.F[k], 'inliers': vm.masks[k], 'verified': vm.verified[k], **{q: v[k] for q, v in refit.items()}}
                 np.savez(os.path.join(args.out, f'{k:05d}_{stem}.npz'), matches=res[0], kpts1=res[1], kpts2=res[2], scores=res[3], **extra)
         if vm is not None:
             print(f'{int(vm.verified.sum())} of {len(pairs)} pairs verified (thr {args.verify_thr} px, at least {args.min_inliers} inliers), '
-                  f'{sum(int(m.sum()) for m in vm.masks)} inlier matches')
+                  f'{sum(int(m.sum()) for m in vm.masks)} inlier matches'
+                  + (f'; the refit on the inliers (up to {args.verify_refit} rounds) changed {int((vm.rounds > 0).sum())} pairs' if refit else ''))
         if args.keypoints:
             cm = consolidate_matches(pairs, results, args.sc_thres, args.qt_psize, args.qt_dthres, args.qt_unique, device=matcher.device,
                                      keep=None if vm is None else vm.masks)
             write_consolidated(args.keypoints, cm)
             if vm is not None:
-                np.savez(os.path.join(args.keypoints, 'two_view.npz'), pairs=cm.pair_images, F=vm.F, n_inliers=vm.n_inliers, verified=vm.verified)
+                np.savez(os.path.join(args.keypoints, 'two_view.npz'), pairs=cm.pair_images, F=vm.F, n_inliers=vm.n_inliers, verified=vm.verified, **refit)
             print(f'{len(cm.names)} images, {sum(len(k) for k in cm.keypoints)} keypoints, {sum(len(m) for m in cm.matches)} matches as keypoint '
                   f'indices -> {args.keypoints}')
         st = matcher.store

@@ -537,11 +537,15 @@ def ransac_essential(mkpts0, mkpts1, counts, N, K0, K1, pixel_thr=0.5, iters=POS
 FUND_RANSAC_ITERS = 512         # fixed, not adaptive; a positive multiple of 64.  An all-inlier sample of 7 at 50 % outliers: 98 % of the pairs
 
 
-def ransac_fundamental(matches, scores, offsets, N, pixel_thr=1.0, sc_thres=0.25, iters=FUND_RANSAC_ITERS, seed=RANSAC_SEED):
+def ransac_fundamental(matches, scores, offsets, N, pixel_thr=1.0, sc_thres=0.25, iters=FUND_RANSAC_ITERS, seed=RANSAC_SEED, refit=0):
     """Device fundamental-matrix RANSAC for the N pairs of a match list (csrc/fund_solver.h): two-view verification without intrinsics.
     matches fp32 [M,4] pixel rows (x0, y0, x1, y1) sorted by pair, scores fp32 [M] or None, offsets int32 [N+1] on the device.  A row takes
     part iff it is finite and (with scores) scores >= sc_thres.  Returns dict(F fp64 [N,3,3] of Frobenius norm 1 (x1^T F x0 = 0), valid
-    int32 [N], n_inliers int32 [N], inliers uint8 [M], hypothesis int32 [N,2])."""
+    int32 [N], n_inliers int32 [N], inliers uint8 [M], hypothesis int32 [N,2]).
+    refit = R in 1 .. 8: the winner is refitted on its inliers up to R times (normalised eight-point fit, rank 2 enforced, inliers selected
+    again; a candidate with fewer inliers is never taken - the `refit` rule of csrc/fund_solver.h, one more launch); F, n_inliers and
+    inliers are then the refined model's, hypothesis still names the seven-point model that seeded it, and the dict gains rounds int32 [N],
+    the refits accepted per pair (0: the pair's outputs are the seven-point winner's bits)."""
     _need_cuda(matches, offsets)
     dev = matches.device
     M = matches.shape[0]
@@ -556,6 +560,13 @@ def ransac_fundamental(matches, scores, offsets, N, pixel_thr=1.0, sc_thres=0.25
     best = torch.empty(N, 2, dtype=torch.int32, device=dev)
     inl = torch.zeros(max(M, 1), dtype=torch.uint8, device=dev)
     L_ = _lib.lib()
+    if refit:
+        rounds = torch.empty(N, dtype=torch.int32, device=dev)
+        ws = _ws.get('fundamental_lo', L_.gf_fundamental_lo_workspace_bytes(N, M, max(int(iters), 1)), dev)
+        check(L_.gf_fundamental_ransac_lo(_p(m), _p(sc), _p(off), N, M, float(sc_thres), float(pixel_thr), int(iters), int(seed), _p(F), _p(valid),
+                                          _p(nin), _p(best), _p(inl), int(refit), _p(rounds), _p(ws), ws.numel(), _stream()),
+              'gf_fundamental_ransac_lo')
+        return {'F': F, 'valid': valid, 'n_inliers': nin, 'inliers': inl[:M], 'hypothesis': best, 'rounds': rounds}
     ws = _ws.get('fundamental', L_.gf_fundamental_workspace_bytes(N, M, max(int(iters), 1)), dev)
     check(L_.gf_fundamental_ransac(_p(m), _p(sc), _p(off), N, M, float(sc_thres), float(pixel_thr), int(iters), int(seed), _p(F), _p(valid),
                                    _p(nin), _p(best), _p(inl), _p(ws), ws.numel(), _stream()),

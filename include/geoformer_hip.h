@@ -39,7 +39,8 @@ typedef enum { GF_F32 = 0, GF_F16 = 1, GF_BF16 = 2 } gf_dtype;
  * version 3 gives wrong channels) and GF_CONV_PAD16 now states that channels 196 .. 223 are padding; new: GF_CONV_S2, gf_lateral_upsample_add_nhwc. */
 /* Still 4 with gf_pos_encode_ptrs / gf_fine_gather_ptrs and gf_pos_encode_ragged / gf_fine_gather_ragged (with gf_map_record): entries appended at
  * the end change no existing one; a binding that needs them fails at load on the missing symbol (geoformer_amd/_lib.py binds every name).
- * Likewise with the gf_keypoint_* entries, gf_fundamental_*, gf_linear_rows, gf_index_rows and gf_fine_rows*. */
+ * Likewise with the gf_keypoint_* entries, gf_fundamental_* (gf_fundamental_ransac_lo and its workspace query included), gf_linear_rows,
+ * gf_index_rows and gf_fine_rows*. */
 #define GF_ABI_VERSION 4
 int gf_abi_version(void);
 const char* gf_last_error(void);
@@ -704,6 +705,21 @@ size_t gf_fundamental_workspace_bytes(int N, int M, int iters);
 int gf_fundamental_ransac(const float* matches, const float* scores, const int32_t* offsets, int N, int M, float sc_thres,
                           float pixel_thr, int iters, uint32_t seed, double* F, int32_t* valid, int32_t* n_inliers, int32_t* best,
                           uint8_t* inliers, void* workspace, size_t workspace_bytes, void* stream);
+/*   gf_fundamental_ransac_lo
+ *     gf_fundamental_ransac followed by a refit of every pair's winner on its inliers, on the device (one more launch, still no host
+ *     synchronisation): up to refit_rounds times a normalised eight-point fit on the current inlier set (normal matrix summed in a fixed
+ *     order, its smallest eigenvector by cyclic Jacobi with fixed sweep counts, rank 2 enforced), the inliers selected again over all rows
+ *     that take part with the same pixel_thr, the candidate accepted iff it has at least as many inliers; stops at a rejected candidate, a
+ *     failed fit, an unchanged set or fewer than 8 inliers.  The rule is the `refit` entry of geoformer_amd/csrc/fund_solver.h, bit-exact
+ *     against the host build like everything above.  No Sampson re-weighting, no planar-degeneracy test, no adaptive stop.
+ *     refit_rounds: 0 .. 8, anything else is GF_ERR_INVALID_ARGUMENT; 0 is exactly gf_fundamental_ransac, with rounds all 0.
+ *     rounds int32 [N]: the refits accepted for the pair; 0 means F, n_inliers and inliers are the seven-point winner's, bit for bit.
+ *     n_inliers never decreases through a refit.  best keeps naming the seven-point (hypothesis, root) that seeded the result.
+ *     workspace: gf_fundamental_lo_workspace_bytes(N, M, iters) bytes. */
+size_t gf_fundamental_lo_workspace_bytes(int N, int M, int iters);
+int gf_fundamental_ransac_lo(const float* matches, const float* scores, const int32_t* offsets, int N, int M, float sc_thres,
+                             float pixel_thr, int iters, uint32_t seed, double* F, int32_t* valid, int32_t* n_inliers, int32_t* best,
+                             uint8_t* inliers, int refit_rounds, int32_t* rounds, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * K3 with a row-address table as the A operand: a gather fused into the GEMM's operand staging.

@@ -13,7 +13,11 @@ form by form, reported as median with min .. max:
   (e) yardstick: extract_features + match_features for the same 120 pairs (host clock).
 The planted maps are pure image shifts - for a fundamental matrix the degenerate case (every seven matches leave a three-dimensional null
 space) - so forms (a) - (c) are also timed on a second load of the same size with an epipolar geometry in it: 120 two-view scenes of
-tests/fund_cases.py's generator (vectorised here), as many rows per pair as the matcher returned, 30 % outliers: forms (f), (g), (h)."""
+tests/fund_cases.py's generator (vectorised here), as many rows per pair as the matcher returned, 30 % outliers: forms (f), (g), (h).
+The refit on the inliers (verify_matches(refit=4): one more launch) is timed beside refit=0 on that second load, in the same process and
+the same alternating windows - forms (i), (j) - and, because exact correspondences leave a refit nothing to improve, on a third load: the
+second one with 0.5 px of Gaussian noise on both images, forms (k) - (n).  For both the accepted rounds per pair and the mean inlier
+count before and after are reported."""
 import argparse
 import ctypes
 import os
@@ -112,13 +116,24 @@ def main(argv=None):
         p1[out] = np.c_[rng.uniform(0, FC.W, int(out.sum())), rng.uniform(0, FC.H, int(out.sum()))]
         m = np.c_[p0, p1].astype(np.float32)
         geo.append((m, m[:, :2], m[:, 2:], np.ones(len(m), np.float32)))
+    noisy = []
+    for g in geo:
+        m = (g[0].astype(np.float64) + rng.normal(0, 0.5, g[0].shape)).astype(np.float32)
+        noisy.append((m, m[:, :2], m[:, 2:], g[3]))
     vg = MT.verify_matches(pairs, geo, device=DEV)
     log(f'second load: {sum(len(g[0]) for g in geo)} rows in {len(geo)} planted two-view scenes, 30 % outliers: verified {int(vg.verified.sum())} of {len(geo)}, '
         f'inliers per pair {int(vg.n_inliers.min())} .. {int(vg.n_inliers.max())}')
 
+    REFIT = 4
+    for name, load in (('second load', geo), ('third load (the second with 0.5 px noise)', noisy)):
+        v0, v4 = MT.verify_matches(pairs, load, device=DEV), MT.verify_matches(pairs, load, device=DEV, refit=REFIT)
+        log(f'{name}, refit={REFIT}: accepted rounds per pair 0 .. {REFIT}: {np.bincount(v4.rounds, minlength=REFIT + 1).tolist()} pairs; mean inliers '
+            f'{v0.n_inliers.mean():.1f} -> {v4.n_inliers.mean():.1f}; verified {int(v0.verified.sum())} -> {int(v4.verified.sum())} of {len(load)}')
+
     h = _lib.lib()
     kern_ms = []
     kern_geo_ms = []
+    kern_refit_ms = {'geo': [], 'noisy0': [], 'noisy4': []}
 
     def timed(fn):
         torch.cuda.synchronize()
@@ -127,11 +142,11 @@ def main(argv=None):
         torch.cuda.synchronize()
         return 1e3 * (time.perf_counter() - t)
 
-    def verify_form(res=None, sink=None):
+    def verify_form(res=None, sink=None, refit=0):
         res, sink = (results, kern_ms) if res is None else (res, sink)
         h.gf_profile_filter(b'fund_ransac')
         h.gf_profile_enable(1)
-        ms = timed(lambda: MT.verify_matches(pairs, res, device=DEV))
+        ms = timed(lambda: MT.verify_matches(pairs, res, device=DEV, refit=refit))
         tot, cnt, work = ctypes.c_double(), ctypes.c_int(), ctypes.c_double()
         h.gf_profile_collect(b'fund_ransac', ctypes.byref(tot), ctypes.byref(cnt), ctypes.byref(work))
         h.gf_profile_enable(0)
@@ -139,8 +154,8 @@ def main(argv=None):
         sink.append(tot.value / max(cnt.value, 1))
         return ms
 
-    def plain_verify_form(res=None):
-        return timed(lambda: MT.verify_matches(pairs, results if res is None else res, device=DEV))
+    def plain_verify_form(res=None, refit=0):
+        return timed(lambda: MT.verify_matches(pairs, results if res is None else res, device=DEV, refit=refit))
 
     # the essential-matrix RANSAC on the same matches (rows at or above the score threshold), inputs resident, the same number of hypotheses
     def pose_inputs(res, cy):
@@ -170,12 +185,17 @@ def main(argv=None):
             return timed(match_pass)
 
     forms = {'verify': verify_form, 'verify_plain': plain_verify_form, 'pose': pose_form, 'consolidate': consolidate_form, 'match': match_form,
-             'geo': lambda: verify_form(geo, kern_geo_ms), 'geo_plain': lambda: plain_verify_form(geo), 'geo_pose': lambda: pose_form(pose_geo_in)}
+             'geo': lambda: verify_form(geo, kern_geo_ms), 'geo_plain': lambda: plain_verify_form(geo), 'geo_pose': lambda: pose_form(pose_geo_in),
+             'geo_refit': lambda: verify_form(geo, kern_refit_ms['geo'], REFIT), 'geo_refit_plain': lambda: plain_verify_form(geo, REFIT),
+             'noisy': lambda: verify_form(noisy, kern_refit_ms['noisy0']), 'noisy_plain': lambda: plain_verify_form(noisy),
+             'noisy_refit': lambda: verify_form(noisy, kern_refit_ms['noisy4'], REFIT), 'noisy_refit_plain': lambda: plain_verify_form(noisy, REFIT)}
     for fn in forms.values():
         for _ in range(2):
             fn()
     kern_ms.clear()
     kern_geo_ms.clear()
+    for v in kern_refit_ms.values():
+        v.clear()
     out = {k: [] for k in forms}
     for _ in range(WINDOWS):
         for k, fn in forms.items():
@@ -190,6 +210,12 @@ def main(argv=None):
     log(line('(f) second load: verify_matches end to end, no events', out['geo_plain'], 'ms'))
     log(line('(g) second load: the three kernels (device events)', kern_geo_ms, 'ms'))
     log(line(f'(h) second load: gf_pose_essential_ransac, {iters} hypotheses (device events)', out['geo_pose'], 'ms'))
+    log(line(f'(i) second load: verify_matches(refit={REFIT}) end to end, no events', out['geo_refit_plain'], 'ms'))
+    log(line(f'(j) second load: the four kernels, refit={REFIT} (device events)', kern_refit_ms['geo'], 'ms'))
+    log(line('(k) third load: verify_matches end to end, no events', out['noisy_plain'], 'ms'))
+    log(line('(l) third load: the three kernels (device events)', kern_refit_ms['noisy0'], 'ms'))
+    log(line(f'(m) third load: verify_matches(refit={REFIT}) end to end, no events', out['noisy_refit_plain'], 'ms'))
+    log(line(f'(n) third load: the four kernels, refit={REFIT} (device events)', kern_refit_ms['noisy4'], 'ms'))
     a, b, c, d, e = (statistics.median(v) for v in (out['verify_plain'], kern_ms, out['pose'], out['consolidate'], out['match']))
     log(f'per pair: verification {1e3 * a / len(pairs):.1f} us end to end, {1e3 * b / len(pairs):.1f} us in its kernels; essential-matrix RANSAC '
         f'{1e3 * c / len(pairs):.1f} us; consolidation {1e3 * d / len(pairs):.1f} us; matching {1e3 * e / len(pairs):.1f} us.  '
@@ -197,6 +223,9 @@ def main(argv=None):
     f, g, hh = (statistics.median(v) for v in (out['geo_plain'], kern_geo_ms, out['geo_pose']))
     log(f'second load, per pair: verification {1e3 * f / len(pairs):.1f} us end to end, {1e3 * g / len(pairs):.1f} us in its kernels; essential-matrix RANSAC '
         f'{1e3 * hh / len(pairs):.1f} us.  verification / matching = {f / e:.4f}; fundamental kernels / essential kernels = {g / hh:.3f}')
+    j, l, n4 = (statistics.median(kern_refit_ms[k]) for k in ('geo', 'noisy0', 'noisy4'))
+    log(f'refit={REFIT}, kernels per pair: second load {1e3 * g / len(pairs):.1f} -> {1e3 * j / len(pairs):.1f} us; third load '
+        f'{1e3 * l / len(pairs):.1f} -> {1e3 * n4 / len(pairs):.1f} us')
 
 
 if __name__ == '__main__':
