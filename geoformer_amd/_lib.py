@@ -164,6 +164,10 @@ SIGNATURES = {
                                   c_void_p, c_void_p]),
     'gf_fine_rows_ragged': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                     c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'gf_abspose_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'gf_abspose_ransac': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_float, c_float, c_int, c_uint32, c_int,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'gf_xyz_lookup': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_long, c_int, c_void_p, c_void_p]),
 }
 
 

@@ -24,6 +24,7 @@ POSE_HOST_LIB = os.path.join(OBJ, 'libpose_host.so')
 WARP_HOST_LIB = os.path.join(OBJ, 'libwarp_host.so')
 KEYPOINT_HOST_LIB = os.path.join(OBJ, 'libkeypoint_host.so')
 FUND_HOST_LIB = os.path.join(OBJ, 'libfund_host.so')
+ABSPOSE_HOST_LIB = os.path.join(OBJ, 'libabspose_host.so')
 
 
 def _headers_digest():
@@ -104,12 +105,21 @@ def build_fund_host(verbose=True):
                            tuple(os.path.join(CSRC, h) for h in ('fund_solver.h', 'solver_common.h', 'keypoint_spec.h', 'gf_hash.h')), verbose)
 
 
+def build_abspose_host(verbose=True):
+    """TEST INFRASTRUCTURE: the serial host form of the absolute-pose RANSAC and of the 3-D map lookup (csrc/host/abspose_host.cpp over
+    csrc/abs_solver.h, the text k_abspose.hip compiles for the device).  Only tests load it."""
+    return _build_host_lib(ABSPOSE_HOST_LIB, 'abspose_host.stamp', os.path.join(CSRC, 'host', 'abspose_host.cpp'),
+                           tuple(os.path.join(CSRC, h) for h in ('abs_solver.h', 'fund_solver.h', 'solver_common.h', 'keypoint_spec.h', 'gf_hash.h')),
+                           verbose)
+
+
 def build(verbose=True, jobs=4):
     os.makedirs(OBJ, exist_ok=True)
     build_pose_host(verbose)
     build_warp_host(verbose)
     build_keypoint_host(verbose)
     build_fund_host(verbose)
+    build_abspose_host(verbose)
     srcs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.hip'))
     hdig = _headers_digest()
     with ThreadPoolExecutor(jobs) as ex:

@@ -34,7 +34,7 @@
 //                     The stage is the KERNEL, not a device function called from one kernel per model: with that one more level of inlining
 //                     the compiler unrolled the seven-point elimination completely (70 -> 106 SGPRs, 82 of them spilled, 36 B
 //                     of scratch reserved per lane); as a kernel template FundModel compiles to what the hand-written fund_score did.
-//                     Instantiated by k_fundamental.hip.  k_pose.hip's pose_score is the same stage written out with per-hypothesis
+//                     Instantiated by k_fundamental.hip and k_abspose.hip (AbsModel: P3P, a pose as two rows of R and t).  k_pose.hip's pose_score is the same stage written out with per-hypothesis
 //                     results: on this kernel's per-block winners it measured 1 - 3.5 % slower (profiles/ransac_tile.txt).
 #pragma once
 #include "gf_common.h"

@@ -1,10 +1,13 @@
-// What the minimal solvers share (pose_solver.h: five points, essential matrix; fund_solver.h: seven points, fundamental matrix), stated
+// What the minimal solvers share (pose_solver.h: five points, essential matrix; fund_solver.h: seven points, fundamental matrix;
+// abs_solver.h: three points, absolute pose), stated
 // once for the device and the host.  Plain C++ in fp64 with contraction off, only + - * / sqrt, fabs and comparisons, so a host build and
 // gfx950 agree bit for bit.  Everything indexed at run time is reached through GsWs (element i at p[i * stride]): the caller decides where
 // it lives - a local array on the host, an LDS tile interleaved across the lanes of a workgroup on the device.
 //
 //   gs_eliminate9<R>   Gauss-Jordan with full pivoting on the R x 9 epipolar system at the start of the workspace, columns swapped in
 //                      place (perm: nibble j = the original column now at position j).
+//   gs_solve<N>        the same elimination on an N x N system with a right-hand side (abs_solver.h: the 6 x 6 normal equations of a
+//                      Gauss-Newton step).
 //   gs_null_basis<R>   the 9 - R null vectors of the eliminated system: vector k has 1 at free column R + k, -A[i][R + k] at pivot column i.
 //   gs_real_roots<D>   real roots of a polynomial of degree D without an eigen-solver: the roots of the k-th derivative separate those of
 //                      the (k-1)-th, so the chain p^(D-1) (linear) .. p^(0) is walked upwards, every sign change between neighbouring
@@ -79,6 +82,42 @@ GS_HD int gs_eliminate9(const GsWs& w, unsigned long long& perm) {
                 for (int j = c; j < 9; ++j) w(9 * r + j) = w(9 * r + j) - f * w(9 * c + j);
         }
     }
+    return 1;
+}
+
+// the N x N system A x = b, augmented: row r is N + 1 doubles at w(off + (N + 1) r + j), b in column N.  Gauss-Jordan with full pivoting as
+// gs_eliminate9 (the same pivot threshold, a NaN wins the pivot search and fails the solve); x goes to w(off_x + i) in the ORIGINAL order of
+// the unknowns.  N <= 15.  Returns 0 for a rank-deficient or non-finite system (x is then unspecified).
+template <int N>
+GS_HD int gs_solve(const GsWs& w, int off, int off_x) {
+    constexpr int C = N + 1;
+    unsigned long long perm = 0xFEDCBA9876543210ull;
+    for (int c = 0; c < N; ++c) {
+        int pr = c, pc = c;
+        double best = -1.0;
+        for (int r = c; r < N; ++r)
+            for (int j = c; j < N; ++j) {
+                const double v = gs_abs_or_inf(w(off + C * r + j));
+                if (v > best) { best = v; pr = r; pc = j; }
+            }
+        if (!(best > 1e-12) || best == (double)INFINITY) return 0;
+        if (pr != c)
+            for (int j = 0; j < C; ++j) { const double tmp = w(off + C * c + j); w(off + C * c + j) = w(off + C * pr + j); w(off + C * pr + j) = tmp; }
+        if (pc != c) {
+            for (int r = 0; r < N; ++r) { const double tmp = w(off + C * r + c); w(off + C * r + c) = w(off + C * r + pc); w(off + C * r + pc) = tmp; }
+            const unsigned long long nc = (perm >> (4 * c)) & 15ull, np = (perm >> (4 * pc)) & 15ull;
+            perm = (perm & ~(15ull << (4 * c)) & ~(15ull << (4 * pc))) | (np << (4 * c)) | (nc << (4 * pc));
+        }
+        const double inv = 1.0 / w(off + C * c + c);
+        for (int j = c; j < C; ++j) w(off + C * c + j) = w(off + C * c + j) * inv;
+        for (int r = 0; r < N; ++r) {
+            if (r == c) continue;
+            const double f = w(off + C * r + c);
+            if (f != 0.0)
+                for (int j = c; j < C; ++j) w(off + C * r + j) = w(off + C * r + j) - f * w(off + C * c + j);
+        }
+    }
+    for (int i = 0; i < N; ++i) w(off_x + (int)((perm >> (4 * i)) & 15ull)) = w(off + C * i + N);
     return 1;
 }
 

@@ -566,6 +566,126 @@ def verify_matches(pairs, results, thr=1.0, min_inliers=15, sc_thres=0.25, iters
     return VerifiedMatches(F, nin, verified, masks, rounds)
 
 
+# ---------------------------------------------------------------------------------------------
+# localisation: a camera pose per query from its matches against database images with known 3-D points, all queries in one call
+# ---------------------------------------------------------------------------------------------
+class LocalizedQueries(NamedTuple):
+    names: list              # the queries, in order of first appearance in the pair list
+    R: np.ndarray            # [Q, 3, 3] float64, x_cam = R X + t in world units (zeros where RANSAC found no model)
+    t: np.ndarray            # [Q, 3] float64
+    n_inliers: np.ndarray    # [Q] int32
+    localized: np.ndarray    # [Q] bool: a model was found and it has at least min_inliers inliers
+    masks: list              # per PAIR: [n_p] bool, the inliers of a localised query's pair; all False otherwise
+    rounds: np.ndarray       # [Q] int32: refits on the inliers accepted per query (zeros without refit)
+
+
+def localize_queries(pairs, results, intrinsics, xyz_maps, thr=12.0, min_inliers=12, sc_thres=0.25, iters=None, device='cuda', refit=0):
+    """Camera poses of query images from their matches against database images whose pixels have known 3-D points - the step the
+    reference's eval_aachen / eval_robotcar / eval_inloc leave to hloc and pycolmap.  pairs: (query, database) paths, results: what
+    match_many returned for them (matches [n, 4] = query x, y, database x, y; scores).  intrinsics[query]: 3 x 3 K of the query in the
+    coordinates of its matches.  xyz_maps[database]: float32 [H, W, 3] array (NaN: no 3-D point) or the path of a .npy holding one, in
+    the coordinates of the database keypoints; each map is uploaded once.  Every database keypoint gets its 3-D point by bilinear lookup
+    (ops.xyz_lookup), all pairs of a query form one problem in pair order, and one absolute-pose RANSAC per query follows
+    (ops.ransac_absolute_pose: P3P hypotheses, reprojection error below thr pixels; the rule is csrc/abs_solver.h) - one upload, the
+    lookup, three launches (four with refit) for all queries, one read back.  localized[q] = a model was found and n_inliers[q] >=
+    min_inliers.  No covisibility clustering, no distortion parameters."""
+    if len(pairs) != len(results):
+        raise ValueError(f'localize_queries: {len(pairs)} pairs but {len(results)} results')
+    P = len(results)
+    ms = [np.asarray(r[0], dtype=np.float32).reshape(-1, 4) for r in results]
+    ss = [np.asarray(r[3], dtype=np.float32).reshape(-1) for r in results]
+    if any(len(m) != len(x) for m, x in zip(ms, ss)):
+        raise ValueError('localize_queries: a result whose matches and scores differ in length')
+    names, qidx = [], {}
+    for q, _ in pairs:
+        if q not in qidx:
+            qidx[q] = len(names)
+            names.append(q)
+    Q = len(names)
+    if P == 0:
+        return LocalizedQueries([], np.zeros((0, 3, 3)), np.zeros((0, 3)), np.zeros(0, np.int32), np.zeros(0, bool), [], np.zeros(0, np.int32))
+    missing = [q for q in names if q not in intrinsics] + [d for _, d in pairs if d not in xyz_maps]
+    if missing:
+        raise ValueError(f'localize_queries: no intrinsics / 3-D map for {missing[0]!r}')
+    order = sorted(range(P), key=lambda p: qidx[pairs[p][0]])          # stable: a query's pairs stay in pair order
+    pair_off = np.concatenate([[0], np.cumsum([len(ms[p]) for p in order])]).astype(np.int32)
+    per_query = np.bincount([qidx[pairs[p][0]] for p in order], weights=[len(ms[p]) for p in order], minlength=Q)
+    query_off = np.concatenate([[0], np.cumsum(per_query)]).astype(np.int32)
+    M = int(pair_off[-1])
+    Ks = np.stack([np.asarray(intrinsics[q], dtype=np.float32).reshape(9) for q in names])
+    rows = np.concatenate([ms[p] for p in order]) if M else np.zeros((0, 4), np.float32)
+    with torch.cuda.device(device):
+        dmaps = {}
+        for _, dname in pairs:
+            if dname not in dmaps:
+                m = xyz_maps[dname]
+                m = np.load(m) if isinstance(m, (str, os.PathLike)) else np.asarray(m)
+                if m.ndim != 3 or m.shape[2] != 3:
+                    raise ValueError(f'localize_queries: the 3-D map of {dname!r} has shape {m.shape}, expected [H, W, 3]')
+                dmaps[dname] = torch.from_numpy(np.ascontiguousarray(m, dtype=np.float32)).to(device)
+        table = np.array([[dmaps[pairs[p][1]].data_ptr(), dmaps[pairs[p][1]].shape[0] | (dmaps[pairs[p][1]].shape[1] << 32)] for p in order],
+                         dtype=np.int64)
+        # one upload: the table first (64-bit words), then everything else as 32-bit words
+        block = np.concatenate([a.reshape(-1).view(np.int32) for a in
+                                (table, np.ascontiguousarray(rows[:, :2]), np.ascontiguousarray(rows[:, 2:]), *[ss[p] for p in order],
+                                 pair_off, query_off, Ks)])
+        d = torch.from_numpy(block).to(device)
+        o = 4 * P
+        tab = d[:o].view(torch.int64).view(P, 2)
+        p2d = d[o:o + 2 * M].view(torch.float32).view(M, 2)
+        pdb = d[o + 2 * M:o + 4 * M].view(torch.float32).view(M, 2)
+        sc = d[o + 4 * M:o + 5 * M].view(torch.float32)
+        poff = d[o + 5 * M:o + 5 * M + P + 1]
+        qoff = d[o + 5 * M + P + 1:o + 5 * M + P + Q + 2]
+        Kd = d[o + 5 * M + P + Q + 2:].view(torch.float32).view(Q, 9)
+        p3d = ops.xyz_lookup(tab, poff, pdb)
+        rs = ops.ransac_absolute_pose(p2d, p3d, sc, qoff, Q, Kd, pixel_thr=thr, sc_thres=sc_thres,
+                                      iters=ops.ABS_RANSAC_ITERS if iters is None else iters, refit=refit)
+        out = torch.cat([rs[k].reshape(-1).view(torch.uint8) for k in ('R', 't', 'valid', 'n_inliers', 'rounds', 'inliers')]).cpu().numpy()
+        del dmaps
+    R = out[:72 * Q].view(np.float64).reshape(Q, 3, 3).copy()
+    t = out[72 * Q:96 * Q].view(np.float64).reshape(Q, 3).copy()
+    valid = out[96 * Q:100 * Q].view(np.int32)
+    nin = out[100 * Q:104 * Q].view(np.int32).copy()
+    rounds = out[104 * Q:108 * Q].view(np.int32).copy()
+    inl = out[108 * Q:].astype(bool)
+    localized = (valid == 1) & (nin >= min_inliers)
+    masks = [None] * P
+    for k, p in enumerate(order):
+        masks[p] = inl[pair_off[k]:pair_off[k + 1]].copy() if localized[qidx[pairs[p][0]]] else np.zeros(len(ms[p]), bool)
+    return LocalizedQueries(names, R, t, nin, localized, masks, rounds)
+
+
+def rotation_to_quaternion(R):
+    """(qw, qx, qy, qz) of a rotation matrix, qw >= 0 - the convention of the localisation benchmarks' submission files."""
+    R = np.asarray(R, dtype=np.float64)
+    k = np.array([[R[0, 0] - R[1, 1] - R[2, 2], 0, 0, 0],
+                  [R[0, 1] + R[1, 0], R[1, 1] - R[0, 0] - R[2, 2], 0, 0],
+                  [R[0, 2] + R[2, 0], R[1, 2] + R[2, 1], R[2, 2] - R[0, 0] - R[1, 1], 0],
+                  [R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1], R[0, 0] + R[1, 1] + R[2, 2]]]) / 3.0
+    w, v = np.linalg.eigh(k)                                          # the eigenvector of the largest eigenvalue: (x, y, z, w)
+    q = v[[3, 0, 1, 2], np.argmax(w)]
+    return q if q[0] >= 0 else -q
+
+
+def read_intrinsics(path):
+    """One line per query: `path fx fy cx cy` (blank lines and '#' lines are skipped; a relative path is relative to the file) ->
+    {path: 3 x 3 K}."""
+    base = os.path.dirname(os.path.abspath(path))
+    out = {}
+    with open(path) as f:
+        for no, line in enumerate(f, 1):
+            parts = line.split()
+            if not parts or parts[0].startswith('#'):
+                continue
+            if len(parts) != 5:
+                raise ValueError(f'{path}:{no}: expected `path fx fy cx cy`, got {len(parts)} fields')
+            fx, fy, cx, cy = (float(v) for v in parts[1:])
+            name = parts[0] if os.path.isabs(parts[0]) else os.path.normpath(os.path.join(base, parts[0]))
+            out[name] = np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1.0]])
+    return out
+
+
 def write_consolidated(out_dir, cm: ConsolidatedMatches):
     """names.txt (one image path per line, line i = image i), keypoints.npz (k00000, ...: [K_i, 2] float32 per image) and matches.npz
     (pairs [P, 2] int32 image indices; m00000, ...: [n_p, 2] int32 keypoint indices per pair)."""
@@ -646,6 +766,26 @@ def estimate_fundamental(matches, thr=1.0, device='cuda', refit=0):
     return rs['F'][0].cpu().numpy(), rs['inliers'].cpu().numpy().astype(bool)
 
 
+def estimate_absolute_pose(points2d, points3d, K, thr=12.0, refit=0, device='cuda', sample=0):
+    """Absolute-pose (P3P) RANSAC from [n,2] pixels and their [n,3] world points on the device (csrc/abs_solver.h); returns (R, t with
+    x_cam = R X + t, inlier mask) or None.  refit: up to that many Gauss-Newton refits of the winner on its inliers (0 .. 8).  sample: the
+    problem index the hypotheses are drawn for (the draw of hypothesis t depends on (seed, problem, t)): the pose of problem q of a
+    larger launch, as localize_queries makes it, is reproduced with sample=q."""
+    if len(points2d) != len(points3d):
+        raise ValueError(f'estimate_absolute_pose: {len(points2d)} 2-D points but {len(points3d)} 3-D points')
+    if len(points2d) < 4:
+        return None
+    n, q = len(points2d), int(sample)
+    a = torch.as_tensor(np.asarray(points2d), dtype=torch.float32, device=device).reshape(n, 2)
+    b = torch.as_tensor(np.asarray(points3d), dtype=torch.float32, device=device).reshape(n, 3)
+    offsets = torch.tensor([0] * (q + 1) + [n], dtype=torch.int32, device=device)
+    rs = ops.ransac_absolute_pose(a, b, None, offsets, q + 1, torch.as_tensor(np.asarray(K), dtype=torch.float32).reshape(3, 3), pixel_thr=thr,
+                                  refit=refit)
+    if int(rs['valid'][q]) == 0:
+        return None
+    return rs['R'][q].cpu().numpy(), rs['t'][q].cpu().numpy(), rs['inliers'].cpu().numpy().astype(bool)
+
+
 def corner_error(H_pred, H_gt, w, h):
     corners = np.array([[0, 0, 1], [0, h - 1, 1], [w - 1, 0, 1], [w - 1, h - 1, 1.0]])
     a = corners @ np.asarray(H_gt).T
@@ -721,6 +861,7 @@ def eval_hpatches(matcher, data_root, ransac_thres=3, thres=(1, 3, 5, 10), scale
 #   python -m geoformer_amd.matcher pairs LIST | --all-pairs DIR  [--out DIR] [--batch B] [--cache-gb G] [--pad [--pad-waste R]]   (no reference counterpart)
 #                                         [--keypoints DIR [--sc-thres S] [--qt-psize P] [--qt-dthres D] [--no-qt-unique]]   (process_matches_and_keypoints_exporth5)
 #                                         [--verify [--verify-thr T] [--min-inliers K] [--verify-refit [R]]]   (two-view verification: fundamental-matrix RANSAC per pair)
+#   python -m geoformer_amd.matcher localize LIST --xyz DIR --intrinsics FILE [--out FILE] [--thr T] [--min-inliers K] [--refit [R]]   (hloc's localize_sfm / localize_inloc)
 # ---------------------------------------------------------------------------------------------
 def build_parser():
     """Defaults follow the reference per sub-command: `match` = inference.py:107 (imsize 640, matches scaled back to the
@@ -772,11 +913,28 @@ def build_parser():
     q.add_argument('--verify-refit', type=int, nargs='?', const=4, default=0, metavar='R',
                    help='with --verify: refit every pair\'s model on its inliers up to R times (1 .. 8; the bare flag: 4) and select the inliers '
                         'again; each .npz of --out and two_view.npz gain refit_rounds')
-    for p in (h, q):
+    loc = sub.add_parser('localize', help='camera poses of query images from their matches against database images with 3-D maps')
+    loc.add_argument('list', help='text file with `query database` image paths per line (relative paths: relative to the file)')
+    loc.add_argument('--xyz', metavar='DIR', required=True,
+                     help="the 3-D map of a database image: DIR/<its path relative to the list>.npy, float32 [H, W, 3] in the coordinates of "
+                          'its keypoints (the original image unless --no-match-upscale), NaN where a pixel has no 3-D point')
+    loc.add_argument('--intrinsics', metavar='FILE', required=True, help='one line per query: path fx fy cx cy')
+    loc.add_argument('--out', default=None, help='file with one line per localised query: path qw qx qy qz tx ty tz (x_cam = R X + t)')
+    loc.add_argument('--thr', type=float, default=12.0, help='inlier threshold, reprojection error in pixels')
+    loc.add_argument('--min-inliers', type=int, default=12, help='a query with fewer inliers is not localised')
+    loc.add_argument('--sc-thres', type=float, default=0.25, help='matches scoring below this take no part')
+    loc.add_argument('--refit', type=int, nargs='?', const=4, default=0, metavar='R',
+                     help='refit every pose on its inliers up to R times (1 .. 8; the bare flag: 4) and select the inliers again')
+    loc.add_argument('--batch', type=int, default=8, help='pairs of equal shapes matched per model call')
+    loc.add_argument('--imsize', type=int, default=640)
+    loc.add_argument('--no-match-upscale', action='store_true')
+    loc.add_argument('--pad', action='store_true', help='let pairs of unequal shapes share a batch (as `pairs --pad`)')
+    loc.add_argument('--pad-waste', type=float, default=None, metavar='R', help='with --pad: as `pairs --pad-waste`')
+    for p in (h, q, loc):
         p.add_argument('--cache-gb', type=float, default=None,
                        help='byte budget of the feature store in GB: least recently used images are dropped and extracted again when '
                             'needed (default: unbounded for `pairs`, 2 for `hpatches --reuse-features`)')
-    for p in (m, h, q):
+    for p in (m, h, q, loc):
         p.add_argument('--ckpt', default=None)
         p.add_argument('--match-threshold', type=float, default=0.2)
         p.add_argument('--precision', choices=PRECISIONS, default='fp16',
@@ -791,7 +949,7 @@ def build_parser():
 
 
 def main(argv=None):
-    """`python -m geoformer_amd.matcher match|hpatches|pairs ...` (arguments: build_parser)."""
+    """`python -m geoformer_amd.matcher match|hpatches|pairs|localize ...` (arguments: build_parser)."""
     args = build_parser().parse_args(argv)
     world = int(os.environ.get('WORLD_SIZE', '1'))
     local = int(os.environ.get('LOCAL_RANK', '0'))
@@ -833,6 +991,21 @@ def main(argv=None):
                   f'indices -> {args.keypoints}')
         st = matcher.store
         print(f'{matcher.name}: {len(pairs)} pairs, {sum(len(r[0]) for r in results)} matches, {st.extractions} extractions, {st.hits} store hits')
+    elif args.cmd == 'localize':
+        pairs = read_pair_list(args.list)
+        base = os.path.dirname(os.path.abspath(args.list))
+        results = matcher.match_many(pairs, batch=args.batch, pad=args.pad, max_waste=args.pad_waste)
+        xyz = {d: os.path.join(args.xyz, os.path.relpath(d, base) + '.npy') for _, d in pairs}
+        lq = localize_queries(pairs, results, read_intrinsics(args.intrinsics), xyz, args.thr, args.min_inliers, args.sc_thres,
+                              device=matcher.device, refit=args.refit)
+        if args.out:
+            with open(args.out, 'w') as f:
+                for k, name in enumerate(lq.names):
+                    if lq.localized[k]:
+                        f.write(' '.join([os.path.relpath(name, base)] + [repr(float(v)) for v in (*rotation_to_quaternion(lq.R[k]), *lq.t[k])]) + '\n')
+        print(f'{int(lq.localized.sum())} of {len(lq.names)} queries localised (thr {args.thr} px, at least {args.min_inliers} inliers) from '
+              f'{len(pairs)} pairs'
+              + (f'; the refit on the inliers (up to {args.refit} rounds) changed {int((lq.rounds > 0).sum())} queries' if args.refit else ''))
     elif args.cmd == 'match':
         res = matcher(args.im1, args.im2)
         print(f'{matcher.name}: {len(res[0])} matches')

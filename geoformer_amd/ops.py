@@ -574,6 +574,82 @@ def ransac_fundamental(matches, scores, offsets, N, pixel_thr=1.0, sc_thres=0.25
     return {'F': F, 'valid': valid, 'n_inliers': nin, 'inliers': inl[:M], 'hypothesis': best}
 
 
+ABS_RANSAC_ITERS = 512          # fixed, not adaptive; a positive multiple of 64.  An all-inlier sample of 3 at 70 % outliers: 1 - 1e-6 of the queries
+
+
+def ransac_absolute_pose(p2d, p3d, scores, offsets, N, K, pixel_thr=12.0, sc_thres=0.25, iters=ABS_RANSAC_ITERS, seed=RANSAC_SEED, refit=0):
+    """Device absolute-pose RANSAC for the N queries of a 2-D - 3-D correspondence list (csrc/abs_solver.h): localisation.
+    p2d fp32 [M,2] query pixels and p3d fp32 [M,3] world points, sorted by query, scores fp32 [M] or None, offsets int32 [N+1] on the
+    device, K [N,3,3] (or [3,3] for all).  A row takes part iff it is finite and (with scores) scores >= sc_thres.  P3P hypotheses,
+    inliers by reprojection error below pixel_thr.  Returns dict(R fp64 [N,3,3], t fp64 [N,3] with x_cam = R X + t, valid int32 [N],
+    n_inliers int32 [N], inliers uint8 [M], hypothesis int32 [N,2], rounds int32 [N]).
+    refit = R in 1 .. 8: the winner is refitted on its inliers up to R times (three Gauss-Newton steps on the reprojection error, inliers
+    selected again; a candidate with fewer inliers is never taken - the `refit` rule of csrc/abs_solver.h, one more launch); rounds
+    counts the refits accepted per query (0: the query's outputs are the P3P winner's bits)."""
+    _need_cuda(p2d, p3d, offsets)
+    dev = p2d.device
+    M = p2d.shape[0]
+    a = _contig(p2d.float().reshape(M, 2)) if M else torch.zeros(1, 2, dtype=torch.float32, device=dev)
+    b = _contig(p3d.float().reshape(M, 3)) if M else torch.zeros(1, 3, dtype=torch.float32, device=dev)
+    if p3d.shape[0] != M:
+        raise ValueError(f'ransac_absolute_pose: {M} 2-D points but {p3d.shape[0]} 3-D points')
+    sc = None if scores is None or M == 0 else _contig(scores.float())
+    off = _contig(offsets.to(device=dev, dtype=torch.int32))
+    if off.numel() != N + 1:
+        raise ValueError(f'ransac_absolute_pose: offsets has {off.numel()} entries for N = {N}')
+    Kt = torch.as_tensor(K, dtype=torch.float32, device=dev)
+    k = _contig((Kt.reshape(1, 9).expand(max(N, 1), 9) if Kt.numel() == 9 else Kt.reshape(max(N, 1), 9)).clone())
+    rows = max(N, 1)                # (N <= 0 is the entry point's error to report: it gets real pointers)
+    R = torch.empty(rows, 3, 3, dtype=torch.float64, device=dev)
+    t = torch.empty(rows, 3, dtype=torch.float64, device=dev)
+    valid = torch.empty(rows, dtype=torch.int32, device=dev)
+    nin = torch.empty(rows, dtype=torch.int32, device=dev)
+    best = torch.empty(rows, 2, dtype=torch.int32, device=dev)
+    rounds = torch.empty(rows, dtype=torch.int32, device=dev)
+    inl = torch.zeros(max(M, 1), dtype=torch.uint8, device=dev)
+    L_ = _lib.lib()
+    ws = _ws.get('abspose', L_.gf_abspose_workspace_bytes(N, M, max(int(iters), 1)), dev)
+    check(L_.gf_abspose_ransac(_p(a), _p(b), _p(sc), _p(off), N, M, _p(k), float(sc_thres), float(pixel_thr), int(iters), int(seed), int(refit),
+                               _p(R), _p(t), _p(valid), _p(nin), _p(best), _p(rounds), _p(inl), _p(ws), ws.numel(), _stream()),
+          'gf_abspose_ransac')
+    return {'R': R, 't': t, 'valid': valid, 'n_inliers': nin, 'inliers': inl[:M], 'hypothesis': best, 'rounds': rounds}
+
+
+def xyz_map_table(maps, device):
+    """The device table of gf_xyz_lookup for a list of fp32 [H, W, 3] device tensors (None: a pair without a map) -> int64 [P, 2] tensor
+    (the address, then h | w << 32).  The caller keeps the maps alive until the lookup has run."""
+    rec = []
+    for m in maps:
+        if m is None:
+            rec.append((0, 0))
+            continue
+        if m.dtype != torch.float32 or m.dim() != 3 or m.shape[2] != 3 or not m.is_contiguous() or not m.is_cuda:
+            raise ValueError('xyz_map_table: a map must be a contiguous fp32 [H, W, 3] tensor on the device')
+        rec.append((m.data_ptr(), int(m.shape[0]) | (int(m.shape[1]) << 32)))
+    return torch.tensor(rec, dtype=torch.int64).reshape(-1, 2).to(device)
+
+
+def xyz_lookup(table, pair_offsets, pts, pts_stride=None):
+    """3-D points of database keypoints (csrc/abs_solver.h: as_xyz_sample): table from xyz_map_table (P records), pair_offsets int32
+    [P+1] on the device, pts fp32 [M,2] (x, y) - or any fp32 tensor whose row i starts pts_stride floats after row i - 1, as the
+    columns 2:4 of a match list.  Returns fp32 [M,3]; NaN where the keypoint is outside its map, next to a pixel without a 3-D point,
+    or in no pair."""
+    _need_cuda(table, pair_offsets, pts)
+    dev = pts.device
+    M, P = pts.shape[0], table.shape[0]
+    out = torch.empty(M, 3, dtype=torch.float32, device=dev)
+    if M == 0 or P == 0:
+        return out.fill_(float('nan'))
+    if pts.dtype != torch.float32 or pts.stride(-1) != 1:
+        raise ValueError('xyz_lookup: pts must be fp32 with unit stride along a row')
+    stride = int(pts.stride(0)) if pts_stride is None else int(pts_stride)
+    off = _contig(pair_offsets.to(device=dev, dtype=torch.int32))
+    if off.numel() != P + 1:
+        raise ValueError(f'xyz_lookup: pair_offsets has {off.numel()} entries for {P} maps')
+    check(_lib.lib().gf_xyz_lookup(_p(table), P, _p(off), _p(pts), stride, M, _p(out), _stream()), 'gf_xyz_lookup')
+    return out
+
+
 def epipolar_errors(mkpts0, mkpts1, m_bids, T_0to1, K0, K1):
     """Squared symmetric epipolar distance of every match under E = [t]x R of its pair's T_0to1 (metrics.py:30-69), fp32 [M]."""
     _need_cuda(mkpts0, mkpts1, m_bids, T_0to1)

@@ -40,7 +40,7 @@ typedef enum { GF_F32 = 0, GF_F16 = 1, GF_BF16 = 2 } gf_dtype;
 /* Still 4 with gf_pos_encode_ptrs / gf_fine_gather_ptrs and gf_pos_encode_ragged / gf_fine_gather_ragged (with gf_map_record): entries appended at
  * the end change no existing one; a binding that needs them fails at load on the missing symbol (geoformer_amd/_lib.py binds every name).
  * Likewise with the gf_keypoint_* entries, gf_fundamental_* (gf_fundamental_ransac_lo and its workspace query included), gf_linear_rows,
- * gf_index_rows and gf_fine_rows*. */
+ * gf_index_rows, gf_fine_rows*, gf_abspose_* and gf_xyz_lookup (with gf_xyz_map). */
 #define GF_ABI_VERSION 4
 int gf_abi_version(void);
 const char* gf_last_error(void);
@@ -763,6 +763,48 @@ int gf_fine_rows_ragged(const gf_map_record* f0_table, const gf_map_record* f1_t
                         const void* feat_c1, int L, int S, int CC, const int64_t* b_ids, const int64_t* i_ids,
                         const int64_t* j_ids, int M, int w0c, int w1c, int stride, int window, uint64_t* win_rows,
                         uint64_t* coarse_rows, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Localising query images: absolute-pose (P3P) RANSAC over 2-D - 3-D correspondences, one problem per query
+ * (the step eval_aachen.py, eval_robotcar.py and eval_inloc.py leave to hloc and pycolmap; the reference has no code for it).  pycolmap
+ * parity is unpinned; the algorithm is the one stated in geoformer_amd/csrc/abs_solver.h (box conditioning of the 3-D points, Grunert's P3P,
+ * reprojection inliers in pixels, an optional Gauss-Newton refit on the inliers), which also compiles for the host
+ * (csrc/host/abspose_host.cpp): bit-exact against that build.
+ *   gf_abspose_ransac
+ *     p2d fp32 [M,2] (u, v in query pixels), p3d fp32 [M,3] (world units), scores fp32 [M] or NULL, offsets int32 [N + 1] in DEVICE memory
+ *     (ascending, first 0, last M: the rows of query n; entries are clamped into [0, M] before use), K fp32 [N,9] (row-major 3 x 3 per
+ *     query; K[0], K[2], K[4], K[5] are used).  A row takes part iff its five numbers are finite and, with scores, its score is not NaN
+ *     and >= sc_thres.
+ *     iters: FIXED number of hypotheses per query, a positive multiple of 64; hypothesis t of query n draws its rows from (seed, n, t).
+ *     N > 0 and N * (iters / 64) <= 16777216 (the workgroups of one launch); pixel_thr > 0; anything else is GF_ERR_INVALID_ARGUMENT.
+ *     refit_rounds: 0 .. 8, anything else is GF_ERR_INVALID_ARGUMENT.  0: the P3P winner and nothing else (three launches).  R > 0: one
+ *     more launch refits the winner on its inliers up to R times (three Gauss-Newton steps on the reprojection error, sums in a fixed
+ *     order, inliers selected again, the candidate accepted iff it has at least as many inliers).
+ *     outputs: R fp64 [N,9] and t fp64 [N,3] with x_cam = R X + t in world units (zeros when not valid), valid int32 [N] (1 iff at least
+ *     4 rows take part, their 3-D box has an extent and a hypothesis produced a solution), n_inliers int32 [N], best int32 [N,2]
+ *     (hypothesis, root of the seeding sample; -1), rounds int32 [N] (refits accepted; 0: every output is the P3P winner's), inliers uint8
+ *     [M] (point in front of the camera and squared reprojection error < pixel_thr^2; filtered rows 0).
+ *     workspace: gf_abspose_workspace_bytes(N, M, iters) bytes.  No host synchronisation, bit-identical from run to run.
+ *   gf_xyz_lookup
+ *     the 3-D side of the list: xyz fp32 [M,3] = the 3-D map of row i's pair sampled at the row's database keypoint.  table: P records in
+ *     DEVICE memory, the map of pair p as [h][w][3] fp32 (a pixel without a 3-D point is NaN; base NULL: a pair without a map);
+ *     pair_offsets int32 [P + 1] on the device (the rows of pair p; a row inside no pair gets NaN); the keypoint of row i is
+ *     (pts[pts_stride * i], pts[pts_stride * i + 1]) = (x, y) with integer coordinates at pixel centres.  Bilinear over the four
+ *     neighbours in fp64, rounded once; NaN when the point lies outside [0, w - 1] x [0, h - 1] or a neighbour is not finite.
+ *     The table and the maps must stay valid until the launch has run - stream order suffices.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct gf_xyz_map {
+    const float* base;     /* element [0][0][0] of the map, in DEVICE memory */
+    int h, w;              /* its extent */
+} gf_xyz_map;              /* 16 bytes: the address, then h | (w << 32) */
+
+size_t gf_abspose_workspace_bytes(int N, int M, int iters);
+int gf_abspose_ransac(const float* p2d, const float* p3d, const float* scores, const int32_t* offsets, int N, int M, const float* K,
+                      float sc_thres, float pixel_thr, int iters, uint32_t seed, int refit_rounds, double* R, double* t, int32_t* valid,
+                      int32_t* n_inliers, int32_t* best, int32_t* rounds, uint8_t* inliers, void* workspace, size_t workspace_bytes,
+                      void* stream);
+int gf_xyz_lookup(const gf_xyz_map* table, int P, const int32_t* pair_offsets, const float* pts, long pts_stride, int M, float* xyz,
+                  void* stream);
 
 #ifdef __cplusplus
 }
