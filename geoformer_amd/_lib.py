@@ -168,6 +168,12 @@ SIGNATURES = {
     'gf_abspose_ransac': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_float, c_float, c_int, c_uint32, c_int,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     'gf_xyz_lookup': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_long, c_int, c_void_p, c_void_p]),
+    'gf_track_link': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'gf_track_flatten': (c_int, [c_void_p, c_int, c_void_p]),
+    'gf_triangulate_workspace_bytes': (c_size_t, [c_int, c_int]),
+    'gf_triangulate': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, ctypes.c_double, c_int, c_int,
+                               c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                               c_void_p]),
 }
 
 

@@ -25,6 +25,7 @@ WARP_HOST_LIB = os.path.join(OBJ, 'libwarp_host.so')
 KEYPOINT_HOST_LIB = os.path.join(OBJ, 'libkeypoint_host.so')
 FUND_HOST_LIB = os.path.join(OBJ, 'libfund_host.so')
 ABSPOSE_HOST_LIB = os.path.join(OBJ, 'libabspose_host.so')
+TRI_HOST_LIB = os.path.join(OBJ, 'libtri_host.so')
 
 
 def _headers_digest():
@@ -113,6 +114,14 @@ def build_abspose_host(verbose=True):
                            verbose)
 
 
+def build_tri_host(verbose=True):
+    """TEST INFRASTRUCTURE and CPU reference: the serial host form of the track building and the triangulation (csrc/host/tri_host.cpp over
+    csrc/tri_solver.h, the text k_triangulate.hip compiles for the device).  Only tests and tools/triangulate_probe.py load it."""
+    return _build_host_lib(TRI_HOST_LIB, 'tri_host.stamp', os.path.join(CSRC, 'host', 'tri_host.cpp'),
+                           tuple(os.path.join(CSRC, h) for h in ('tri_solver.h', 'abs_solver.h', 'fund_solver.h', 'solver_common.h',
+                                                                 'keypoint_spec.h', 'gf_hash.h')), verbose)
+
+
 def build(verbose=True, jobs=4):
     os.makedirs(OBJ, exist_ok=True)
     build_pose_host(verbose)
@@ -120,6 +129,7 @@ def build(verbose=True, jobs=4):
     build_keypoint_host(verbose)
     build_fund_host(verbose)
     build_abspose_host(verbose)
+    build_tri_host(verbose)
     srcs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.hip'))
     hdig = _headers_digest()
     with ThreadPoolExecutor(jobs) as ex:

@@ -696,6 +696,218 @@ def write_consolidated(out_dir, cm: ConsolidatedMatches):
     np.savez(os.path.join(out_dir, 'matches.npz'), pairs=cm.pair_images, **{f'm{q:05d}': m for q, m in enumerate(cm.matches)})
 
 
+def read_consolidated(in_dir) -> ConsolidatedMatches:
+    """The inverse of write_consolidated: names.txt, keypoints.npz and matches.npz under in_dir -> ConsolidatedMatches."""
+    with open(os.path.join(in_dir, 'names.txt')) as f:
+        names = [line.rstrip('\n') for line in f if line.rstrip('\n')]
+    with np.load(os.path.join(in_dir, 'keypoints.npz')) as kz:
+        keypoints = [np.asarray(kz[f'k{i:05d}'], dtype=np.float32).reshape(-1, 2) for i in range(len(names))]
+    with np.load(os.path.join(in_dir, 'matches.npz')) as mz:
+        pair_images = np.asarray(mz['pairs'], dtype=np.int32).reshape(-1, 2)
+        matches = [np.asarray(mz[f'm{q:05d}'], dtype=np.int32).reshape(-1, 2) for q in range(len(pair_images))]
+    return ConsolidatedMatches(names, keypoints, pair_images, matches)
+
+
+def quaternion_to_rotation(q):
+    """The rotation matrix of (qw, qx, qy, qz), normalised first: the inverse of rotation_to_quaternion."""
+    w, x, y, z = np.asarray(q, dtype=np.float64) / np.linalg.norm(q)
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+
+
+def read_poses(path):
+    """One line per image: `path qw qx qy qz tx ty tz` with x_cam = R X + t, the format `localize --out` writes (blank lines and '#' lines
+    are skipped; a relative path is relative to the file) -> {path: (R 3 x 3, t [3])}."""
+    base = os.path.dirname(os.path.abspath(path))
+    out = {}
+    with open(path) as f:
+        for no, line in enumerate(f, 1):
+            parts = line.split()
+            if not parts or parts[0].startswith('#'):
+                continue
+            if len(parts) != 8:
+                raise ValueError(f'{path}:{no}: expected `path qw qx qy qz tx ty tz`, got {len(parts)} fields')
+            v = np.array([float(x) for x in parts[1:]])
+            if not np.all(np.isfinite(v)) or not np.linalg.norm(v[:4]) > 0:
+                raise ValueError(f'{path}:{no}: the pose is not finite or its quaternion is zero')
+            name = parts[0] if os.path.isabs(parts[0]) else os.path.normpath(os.path.join(base, parts[0]))
+            out[name] = (quaternion_to_rotation(v[:4]), v[4:].copy())
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
+# triangulation of the database images from their known poses (hloc's triangulation / COLMAP's point_triangulator in
+# localize_sfm_helper.py:reconstruct_database_pairs), and localisation against the triangulated points
+# ---------------------------------------------------------------------------------------------
+class TriangulatedTracks(NamedTuple):
+    points: np.ndarray       # [T_valid, 3] float64: the triangulated 3-D points, in world units
+    errors: np.ndarray       # [T_valid] float64: root of the mean squared reprojection error of a point's inliers, in pixels
+    obs_offsets: np.ndarray  # [T_valid + 1] int32: the inlier observations of point k are obs_offsets[k] : obs_offsets[k + 1]
+    obs_image: np.ndarray    # [N] int32: index into the ConsolidatedMatches' names
+    obs_keypoint: np.ndarray  # [N] int32: index into that image's keypoints
+    point_of_keypoint: list  # per image: [K_i] int32, the point a keypoint is an inlier observation of; -1: none
+    n_tracks: int            # connected components of the match graph with at least two keypoints
+    n_conflict: int          # of them: tracks in which an image occurs twice (not triangulated)
+    n_rejected: int          # of them: tracks without a conflict that ended without a point (no solution, or fewer than min_obs inliers)
+
+
+def triangulate(cm: ConsolidatedMatches, intrinsics, poses, thr=4.0, min_angle=1.5, min_obs=2, refit=2, device='cuda') -> TriangulatedTracks:
+    """3-D points for the tracks of a ConsolidatedMatches from known camera poses, on the device.  intrinsics[name]: 3 x 3 K in the
+    coordinates of the keypoints; poses[name] = (R, t) with x_cam = R X + t (what localize_queries returns and read_poses reads).  Images
+    without an entry in poses take no part.  A track is a connected component of the graph whose nodes are keypoints and whose edges are
+    matches (ops.build_tracks); a track with the same image twice is a conflict and is left out; every other track gets the best two-view
+    midpoint among its observation pairs (rays meeting at min_angle degrees or more; inliers: reprojection error below thr pixels), refitted
+    on its inliers up to `refit` times (ops.triangulate_tracks; the rule is csrc/tri_solver.h), and is kept with at least min_obs
+    inliers.  refit defaults to 2 here (0 in ops): a two-ray midpoint alone is a poor point for a long track.  Before the upload the world
+    origin is moved to the centre of the bounding box of the camera centres (fp64), and the points are moved back afterwards.  One upload,
+    one read back.  No bundle adjustment, no re-triangulation or merging of tracks, no splitting of conflict tracks, no distortion."""
+    n, kp_off, K, R, t, origin, ids, id_off, kps, pim = _triangulation_inputs(cm, intrinsics, poses)
+    n_nodes, P, E = int(kp_off[-1]), len(cm.matches), len(ids)
+    empty = _assemble_tracks(n, kp_off, 0, *([np.zeros(0)] * 4), np.zeros(1, np.int32), *([np.zeros(0, np.int32)] * 2), np.zeros(0, bool), origin)
+    if n_nodes == 0 or E == 0:
+        return empty
+    # one upload: the fp64 words first, then everything else as 32-bit words
+    block = np.concatenate([a.reshape(-1).view(np.int32) for a in (np.ascontiguousarray(R), np.ascontiguousarray(t), K, kps, ids, id_off, pim, kp_off)])
+    with torch.cuda.device(device):
+        d = torch.from_numpy(block).to(device)
+        o = 0
+
+        def take(words, dtype, *shape):
+            nonlocal o
+            v = d[o:o + words].view(dtype).view(*shape)
+            o += words
+            return v
+        Rd, td = take(18 * n, torch.float64, n, 9), take(6 * n, torch.float64, n, 3)
+        Kd, kpd = take(9 * n, torch.float32, n, 9), take(2 * n_nodes, torch.float32, n_nodes, 2)
+        idd, iod, pimd, kpod = take(2 * E, torch.int32, E, 2), take(P + 1, torch.int32, P + 1), take(2 * P, torch.int32, P, 2), take(n + 1, torch.int32, n + 1)
+        track_off, obs_image, obs_kp, obs_node = ops.build_tracks(idd, iod, pimd, kpod, n_nodes=n_nodes)
+        T = int(track_off.numel()) - 1
+        if T == 0:
+            return empty
+        rs = ops.triangulate_tracks(track_off, obs_image, kpd[obs_node.long()], Kd, Rd, td, pixel_thr=thr, min_angle_deg=min_angle, min_obs=min_obs,
+                                    refit=refit)
+        out = torch.cat([x.reshape(-1).view(torch.uint8) for x in (rs['X'], rs['err2'], rs['valid'], rs['conflict'], track_off, obs_image, obs_kp,
+                                                                   rs['inliers'])]).cpu().numpy()
+    N = int(obs_image.numel())
+    return _assemble_tracks(n, kp_off, T, out[:24 * T].view(np.float64).reshape(T, 3), out[24 * T:32 * T].view(np.float64),
+                            out[32 * T:36 * T].view(np.int32), out[36 * T:40 * T].view(np.int32), out[40 * T:44 * T + 4].view(np.int32),
+                            out[44 * T + 4:44 * T + 4 + 4 * N].view(np.int32), out[44 * T + 4 + 4 * N:44 * T + 4 + 8 * N].view(np.int32),
+                            out[44 * T + 4 + 8 * N:], origin)
+
+
+def _triangulation_inputs(cm, intrinsics, poses):
+    """What triangulate uploads: (n images, kp_off int32 [n+1], K fp32 [n,9], R fp64 [n,9] and t fp64 [n,3] with NaN for an image without
+    a pose and t moved to the new origin, origin [3], ids int32 [E,2], id_off int32 [P+1], keypoints fp32 [n_nodes,2], pair_images)."""
+    n = len(cm.names)
+    counts = np.array([len(k) for k in cm.keypoints], np.int64)
+    kp_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+    K, R, t = np.zeros((n, 9), np.float32), np.full((n, 9), np.nan), np.full((n, 3), np.nan)
+    K[:, [0, 4, 8]] = 1.0
+    for i, name in enumerate(cm.names):
+        if name not in poses:
+            continue
+        if name not in intrinsics:
+            raise ValueError(f'triangulate: no intrinsics for {name!r}')
+        K[i] = np.asarray(intrinsics[name], dtype=np.float32).reshape(9)
+        R[i] = np.asarray(poses[name][0], dtype=np.float64).reshape(9)
+        t[i] = np.asarray(poses[name][1], dtype=np.float64).reshape(3)
+    posed = np.isfinite(R).all(1) & np.isfinite(t).all(1)
+    origin = np.zeros(3)
+    if posed.any():
+        centres = -np.einsum('nji,nj->ni', R[posed].reshape(-1, 3, 3), t[posed])
+        origin = 0.5 * (centres.min(0) + centres.max(0))
+        t[posed] = t[posed] + np.einsum('nij,j->ni', R[posed].reshape(-1, 3, 3), origin)        # x_cam = R (X' + origin) + t
+    ids = np.concatenate([np.asarray(m, np.int32).reshape(-1, 2) for m in cm.matches]) if len(cm.matches) else np.zeros((0, 2), np.int32)
+    id_off = np.concatenate([[0], np.cumsum([len(m) for m in cm.matches])]).astype(np.int32)
+    kps = np.concatenate([np.asarray(k, np.float32).reshape(-1, 2) for k in cm.keypoints]) if n else np.zeros((0, 2), np.float32)
+    return n, kp_off, K, R, t, origin, ids, id_off, kps, np.asarray(cm.pair_images, np.int32).reshape(-1, 2)
+
+
+def _assemble_tracks(n, kp_off, T, X, err2, valid, conflict, toff, oimg, okp, inl, origin) -> TriangulatedTracks:
+    """The per-track and per-observation outputs of ops.triangulate_tracks -> TriangulatedTracks (points moved back by origin)."""
+    valid, conflict, inl = np.asarray(valid) == 1, np.asarray(conflict) == 1, np.asarray(inl).astype(bool)
+    nv = int(valid.sum())
+    track_of_obs = np.repeat(np.arange(T), np.diff(toff))
+    point_of_track = np.full(T, -1, np.int64)
+    point_of_track[valid] = np.arange(nv)
+    keep = inl & valid[track_of_obs]
+    per_point = np.bincount(point_of_track[track_of_obs[keep]], minlength=nv)
+    pok = np.full(int(kp_off[-1]), -1, np.int32)
+    pok[kp_off[oimg[keep]] + okp[keep]] = point_of_track[track_of_obs[keep]]
+    return TriangulatedTracks(np.asarray(X, np.float64).reshape(T, 3)[valid] + origin, np.sqrt(np.asarray(err2, np.float64)[valid]),
+                              np.concatenate([[0], np.cumsum(per_point)]).astype(np.int32), oimg[keep].astype(np.int32), okp[keep].astype(np.int32),
+                              [pok[kp_off[i]:kp_off[i + 1]].copy() for i in range(n)], int(T), int(conflict.sum()),
+                              int(T - conflict.sum() - nv))
+
+
+def localize_queries_sparse(cm: ConsolidatedMatches, tt: TriangulatedTracks, queries, intrinsics, thr=12.0, min_inliers=12, iters=None, refit=0,
+                            device='cuda') -> LocalizedQueries:
+    """Camera poses of query images against triangulated points: the sparse counterpart of localize_queries for datasets with database
+    poses and no depth.  queries: image names of cm.  For every pair of cm that joins a query and an image with points (the query on either
+    side), the rows are p2d = the query's keypoints, p3d = the point of the other image's keypoint (tt.point_of_keypoint; NaN where it has
+    none, such a row takes no part).  All pairs of a query form one problem in pair order, then ops.ransac_absolute_pose as in
+    localize_queries.  intrinsics[query]: 3 x 3 K.  masks: one per pair of cm ([n_p] bool; all False for a pair that joins no query to
+    points).  Indexing on the host and an existing op: no new kernel."""
+    names = list(dict.fromkeys(queries))
+    Q = len(names)
+    missing = [q for q in names if q not in intrinsics or q not in cm.names]
+    if missing:
+        raise ValueError(f'localize_queries_sparse: no intrinsics for, or no image named {missing[0]!r}')
+    p2d, p3d, query_off, pair_off, used, owner = _sparse_rows(cm, tt, names)
+    masks = [np.zeros(len(m), bool) for m in cm.matches]
+    M = len(p2d)
+    if Q == 0 or M == 0:
+        return LocalizedQueries(names, np.zeros((Q, 3, 3)), np.zeros((Q, 3)), np.zeros(Q, np.int32), np.zeros(Q, bool), masks, np.zeros(Q, np.int32))
+    Ks = np.stack([np.asarray(intrinsics[q], dtype=np.float32).reshape(9) for q in names])
+    block = np.concatenate([a.reshape(-1).view(np.int32) for a in (p2d, p3d, query_off, Ks)])
+    with torch.cuda.device(device):
+        d = torch.from_numpy(block).to(device)
+        rs = ops.ransac_absolute_pose(d[:2 * M].view(torch.float32).view(M, 2), d[2 * M:5 * M].view(torch.float32).view(M, 3), None,
+                                      d[5 * M:5 * M + Q + 1], Q, d[5 * M + Q + 1:].view(torch.float32).view(Q, 9), pixel_thr=thr,
+                                      iters=ops.ABS_RANSAC_ITERS if iters is None else iters, refit=refit)
+        out = torch.cat([rs[k].reshape(-1).view(torch.uint8) for k in ('R', 't', 'valid', 'n_inliers', 'rounds', 'inliers')]).cpu().numpy()
+    R = out[:72 * Q].view(np.float64).reshape(Q, 3, 3).copy()
+    t = out[72 * Q:96 * Q].view(np.float64).reshape(Q, 3).copy()
+    valid = out[96 * Q:100 * Q].view(np.int32)
+    nin = out[100 * Q:104 * Q].view(np.int32).copy()
+    rounds = out[104 * Q:108 * Q].view(np.int32).copy()
+    inl = out[108 * Q:].astype(bool)
+    localized = (valid == 1) & (nin >= min_inliers)
+    for pos, (p, q) in enumerate(zip(used, owner)):
+        if localized[q]:
+            masks[p] = inl[pair_off[pos]:pair_off[pos + 1]].copy()
+    return LocalizedQueries(names, R, t, nin, localized, masks, rounds)
+
+
+def _sparse_rows(cm, tt, names):
+    """The 2-D - 3-D rows of localize_queries_sparse, sorted by query (a query's pairs in pair order): p2d fp32 [M,2], p3d fp32 [M,3] (NaN:
+    the keypoint has no point), query_off int32 [Q+1], pair_off [n+1] (the rows of the n contributing pairs), and per contributing pair
+    its index in cm and its query."""
+    qidx = {q: k for k, q in enumerate(names)}
+    image_q = np.array([qidx.get(nm, -1) for nm in cm.names], np.int64)
+    has_pts = np.array([bool((p >= 0).any()) for p in tt.point_of_keypoint])
+    rows2, rows3, owner, used = [], [], [], []
+    for p in range(len(cm.matches)):
+        i, j = (int(v) for v in cm.pair_images[p])
+        m = np.asarray(cm.matches[p]).reshape(-1, 2)
+        for qs, ds, a, b in ((i, j, 0, 1), (j, i, 1, 0)):
+            if image_q[qs] >= 0 and image_q[ds] < 0 and has_pts[ds]:
+                pt = tt.point_of_keypoint[ds][m[:, b]]
+                x = np.full((len(m), 3), np.nan, np.float32)
+                x[pt >= 0] = tt.points[pt[pt >= 0]]
+                rows2.append(np.asarray(cm.keypoints[qs], np.float32).reshape(-1, 2)[m[:, a]]), rows3.append(x)
+                owner.append(int(image_q[qs])), used.append(p)
+                break
+    order = sorted(range(len(used)), key=lambda k: owner[k])            # stable: a query's pairs stay in pair order
+    lens = [len(rows2[k]) for k in order]
+    pair_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    query_off = np.concatenate([[0], np.cumsum(np.bincount([owner[k] for k in order], weights=lens, minlength=len(names)))]).astype(np.int32)
+    p2d = np.concatenate([rows2[k] for k in order]) if order else np.zeros((0, 2), np.float32)
+    p3d = np.concatenate([rows3[k] for k in order]) if order else np.zeros((0, 3), np.float32)
+    return p2d, p3d, query_off, pair_off, [used[k] for k in order], [owner[k] for k in order]
+
+
 # ---------------------------------------------------------------------------------------------
 # HPatches homography metric
 # ---------------------------------------------------------------------------------------------
@@ -862,6 +1074,7 @@ def eval_hpatches(matcher, data_root, ransac_thres=3, thres=(1, 3, 5, 10), scale
 #                                         [--keypoints DIR [--sc-thres S] [--qt-psize P] [--qt-dthres D] [--no-qt-unique]]   (process_matches_and_keypoints_exporth5)
 #                                         [--verify [--verify-thr T] [--min-inliers K] [--verify-refit [R]]]   (two-view verification: fundamental-matrix RANSAC per pair)
 #   python -m geoformer_amd.matcher localize LIST --xyz DIR --intrinsics FILE [--out FILE] [--thr T] [--min-inliers K] [--refit [R]]   (hloc's localize_sfm / localize_inloc)
+#   python -m geoformer_amd.matcher triangulate KEYPOINTS_DIR --poses FILE --intrinsics FILE [--out FILE.npz] [--thr T] [--min-angle A] [--min-obs K] [--refit [R]]   (hloc's triangulation)
 # ---------------------------------------------------------------------------------------------
 def build_parser():
     """Defaults follow the reference per sub-command: `match` = inference.py:107 (imsize 640, matches scaled back to the
@@ -930,6 +1143,21 @@ def build_parser():
     loc.add_argument('--no-match-upscale', action='store_true')
     loc.add_argument('--pad', action='store_true', help='let pairs of unequal shapes share a batch (as `pairs --pad`)')
     loc.add_argument('--pad-waste', type=float, default=None, metavar='R', help='with --pad: as `pairs --pad-waste`')
+    tri = sub.add_parser('triangulate', help='3-D points for the tracks of a consolidated match directory from known camera poses')
+    tri.add_argument('keypoints', metavar='KEYPOINTS_DIR', help='what `pairs --keypoints DIR` wrote: names.txt, keypoints.npz, matches.npz')
+    tri.add_argument('--poses', metavar='FILE', required=True,
+                     help='one line per database image: path qw qx qy qz tx ty tz (x_cam = R X + t; what `localize --out` writes); images '
+                          'without a line take no part')
+    tri.add_argument('--intrinsics', metavar='FILE', required=True, help='one line per image with a pose: path fx fy cx cy')
+    tri.add_argument('--out', metavar='FILE.npz', default=None,
+                     help='points, errors, obs_offsets, obs_image, obs_keypoint, point_of_keypoint (all images, concatenated in the order of '
+                          'names.txt) and kp_offsets')
+    tri.add_argument('--thr', type=float, default=4.0, help='inlier threshold, reprojection error in pixels')
+    tri.add_argument('--min-angle', type=float, default=1.5, help='smallest triangulation angle of a hypothesis pair, in degrees')
+    tri.add_argument('--min-obs', type=int, default=2, help='a track with fewer inlier observations gets no point (at least 2)')
+    tri.add_argument('--refit', type=int, nargs='?', const=4, default=2, metavar='R',
+                     help='refit every point on its inliers up to R times (0 .. 8; the bare flag: 4; default 2) and select the inliers again')
+    tri.add_argument('--device', default='cuda')
     for p in (h, q, loc):
         p.add_argument('--cache-gb', type=float, default=None,
                        help='byte budget of the feature store in GB: least recently used images are dropped and extracted again when '
@@ -948,9 +1176,38 @@ def build_parser():
     return ap
 
 
+def run_triangulate(args):
+    """The `triangulate` sub-command: names.txt lists the images as the pair list named them, so a relative name in the poses and
+    intrinsics files is looked up both as written and relative to its file."""
+    cm = read_consolidated(args.keypoints)
+    poses, intr = read_poses(args.poses), read_intrinsics(args.intrinsics)
+    for table, path in ((poses, args.poses), (intr, args.intrinsics)):
+        base = os.path.dirname(os.path.abspath(path))
+        for name in cm.names:
+            full = name if os.path.isabs(name) else os.path.normpath(os.path.join(base, name))
+            if name not in table and full in table:
+                table[name] = table[full]
+    tt = triangulate(cm, intr, poses, args.thr, args.min_angle, args.min_obs, args.refit, device=args.device)
+    if args.out:
+        np.savez(args.out, points=tt.points, errors=tt.errors, obs_offsets=tt.obs_offsets, obs_image=tt.obs_image, obs_keypoint=tt.obs_keypoint,
+                 point_of_keypoint=np.concatenate(tt.point_of_keypoint) if tt.point_of_keypoint else np.zeros(0, np.int32),
+                 kp_offsets=np.concatenate([[0], np.cumsum([len(p) for p in tt.point_of_keypoint])]).astype(np.int32))
+    print(f'{len(tt.points)} points from {tt.n_tracks} tracks of {sum(n in poses for n in cm.names)} posed images ({tt.n_conflict} with an image '
+          f'twice, {tt.n_rejected} without a point; thr {args.thr} px, angle >= {args.min_angle} deg, at least {args.min_obs} observations, up '
+          f'to {args.refit} refits); {len(tt.obs_image)} observations, median reprojection error '
+          f'{float(np.median(tt.errors)) if len(tt.errors) else 0.0:.3f} px' + (f' -> {args.out}' if args.out else ''))
+    return tt
+
+
 def main(argv=None):
-    """`python -m geoformer_amd.matcher match|hpatches|pairs|localize ...` (arguments: build_parser)."""
-    args = build_parser().parse_args(argv)
+    """`python -m geoformer_amd.matcher match|hpatches|pairs|localize|triangulate ...` (arguments: build_parser)."""
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    if args.cmd == 'triangulate':                                       # no model: keypoints, matches and poses in, points out
+        if args.min_obs < 2 or not 0 <= args.refit <= 8 or not args.thr > 0:
+            ap.error('triangulate: need --min-obs >= 2, --refit 0 .. 8 and --thr > 0')
+        run_triangulate(args)
+        return
     world = int(os.environ.get('WORLD_SIZE', '1'))
     local = int(os.environ.get('LOCAL_RANK', '0'))
     if world > 1:

@@ -4,6 +4,7 @@ Every function enqueues on torch's current stream and returns device tensors; da
 counts stay on the device (`counts` tensors) until a caller needs their value.
 """
 import ctypes
+import math
 
 import torch
 
@@ -1332,3 +1333,95 @@ def consolidate_keypoints(matches, scores, pair_offsets, pair_images, n_images, 
     if flags & KP_FLAG_COORD_RANGE:
         raise _lib.GeoFormerHipError('consolidate_keypoints: a coordinate lies outside the supported +-2^22 of the quantised mode')
     return keypoints[:K], kp_offsets, ids[:rows], ids_offsets
+
+
+# ---------------------------------------------------------------------------------------------
+# tracks and their triangulation from known poses (csrc/k_triangulate.hip over csrc/tri_solver.h)
+# ---------------------------------------------------------------------------------------------
+TR_FLAG_EDGE_RANGE = 1          # tri_solver.h TR_FLAG_*: bits of gf_track_link's status word
+
+
+def build_tracks(ids, id_off, pair_images, kp_off, n_nodes=None):
+    """The tracks of a keypoint match graph on the device (csrc/tri_solver.h, steps 1 and 2).  Device tensors: ids int32 [E,2] (per-image
+    keypoint indices of every match row), id_off int32 [P+1] (the rows of pair p), pair_images int32 [P,2], kp_off int32 [n_images+1] (the
+    prefix sum of the per-image keypoint counts) - what consolidate_keypoints returns.  Keypoint k of image i is node kp_off[i] + k; a
+    track is a connected component with at least two nodes.  Returns (track_off int32 [T+1], obs_image int32 [N_obs], obs_kp int32
+    [N_obs], obs_node int32 [N_obs]): tracks in ascending order of their smallest node, observations ascending (image-major).
+    gf_track_link (lock-free union-find, one thread per row) and gf_track_flatten; the track list between them and the triangulation is
+    torch's - a stable sort of the nodes by root and scans - with one device-to-host read (the sizes and the status word; one more for
+    kp_off[-1] unless n_nodes, the number of keypoints, is given).  A row naming an image or a keypoint that does not exist raises after
+    that read; nothing wraps."""
+    _need_cuda(ids, id_off, pair_images, kp_off)
+    dev = kp_off.device
+    E, P, n_images = int(ids.shape[0]), int(pair_images.shape[0]), int(kp_off.numel()) - 1
+    if ids.shape != (E, 2) or id_off.shape != (P + 1,) or pair_images.shape != (P, 2) or n_images < 0:
+        raise ValueError('build_tracks: ids [E,2], id_off [P+1], pair_images [P,2], kp_off [n_images+1]')
+    ids_, ido, pim, kpo = (_contig(x.to(torch.int32)) for x in (ids, id_off, pair_images, kp_off))
+    n_nodes = int(kpo[-1]) if n_nodes is None else int(n_nodes)     # (a caller that holds the number of keypoints saves this read)
+    L_ = _lib.lib()
+    parent = torch.empty(max(n_nodes, 1), dtype=torch.int32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    check(L_.gf_track_link(_p(ids_), _p(ido), _p(pim), P, E, _p(kpo), n_images, n_nodes, _p(parent), _p(status), _stream()), 'gf_track_link')
+    check(L_.gf_track_flatten(_p(parent), n_nodes, _stream()), 'gf_track_flatten')
+    parent = parent[:n_nodes]
+    empty = torch.zeros(0, dtype=torch.int32, device=dev)
+    if n_nodes == 0:
+        if int(status[0]) & TR_FLAG_EDGE_RANGE:
+            raise _lib.GeoFormerHipError('build_tracks: a match row names an image or a keypoint that does not exist')
+        return torch.zeros(1, dtype=torch.int32, device=dev), empty, empty.clone(), empty.clone()
+    # nodes by root (stable: ascending inside a component; roots ascend with the component's smallest node), then segment lengths
+    root, order = torch.sort(parent, stable=True)
+    head = torch.ones(n_nodes, dtype=torch.int64, device=dev)
+    head[1:] = (root[1:] != root[:-1]).long()
+    seg = torch.cumsum(head, 0) - 1
+    cnt = torch.zeros(n_nodes, dtype=torch.int64, device=dev).scatter_add_(0, seg, torch.ones_like(seg))
+    keep_obs = cnt[seg] >= 2
+    keep_trk = cnt >= 2
+    sizes = torch.stack([keep_trk.sum(), keep_obs.sum(), status[0].long()]).cpu()          # the one device-to-host read
+    T, n_obs, flags = int(sizes[0]), int(sizes[1]), int(sizes[2])
+    if flags & TR_FLAG_EDGE_RANGE:
+        raise _lib.GeoFormerHipError('build_tracks: a match row names an image or a keypoint that does not exist')
+    obs_node = order[torch.sort((~keep_obs).to(torch.int8), stable=True).indices[:n_obs]].to(torch.int32)
+    lens = cnt[torch.sort((~keep_trk).to(torch.int8), stable=True).indices[:T]]
+    track_off = torch.cat([lens.new_zeros(1), torch.cumsum(lens, 0)]).to(torch.int32)
+    obs_image = (torch.searchsorted(kpo.long(), obs_node.long(), right=True) - 1).clamp_(0, max(n_images - 1, 0)).to(torch.int32)
+    obs_kp = obs_node - kpo[obs_image.long()]
+    return track_off, obs_image, obs_kp, obs_node
+
+
+def triangulate_tracks(track_off, obs_image, obs_uv, K, R, t, pixel_thr=4.0, min_angle_deg=1.5, min_obs=2, refit=0, seed=RANSAC_SEED):
+    """One 3-D point per track from known camera poses, on the device (csrc/tri_solver.h, steps 3 - 9).  track_off int32 [T+1] and
+    obs_image int32 [N_obs] as build_tracks returns them, obs_uv fp32 [N_obs,2] pixels, K [n_images,3,3] (fp32), R [n_images,3,3] and
+    t [n_images,3] (fp64, x_cam = R X + t; NaN: an image without a pose, its observations take no part).  Hypotheses: the two-view
+    midpoint of every pair of a track's observations up to length 11, 64 drawn pairs above; a pair whose rays meet at less than
+    min_angle_deg has no solution (the threshold goes to the device as its cosine, computed here once); inliers by reprojection error
+    below pixel_thr; most inliers win, then the smallest hypothesis.  A track is valid iff no image occurs twice in it (conflict) and its
+    winner has at least min_obs (>= 2) inliers.  refit = R in 1 .. 8: up to R refits of the point on its inliers (three Gauss-Newton steps,
+    inliers selected again, never fewer than before).  Returns dict(X fp64 [T,3] (zeros where not valid), valid, conflict, n_inliers,
+    hypothesis, rounds int32 [T], err2 fp64 [T] (mean squared reprojection error of the inliers), inliers uint8 [N_obs]).  No host
+    synchronisation; bit-identical from run to run."""
+    _need_cuda(track_off, obs_image, obs_uv)
+    dev = track_off.device
+    T, n_obs = int(track_off.numel()) - 1, int(obs_image.numel())
+    if T < 0 or obs_uv.shape != (n_obs, 2):
+        raise ValueError('triangulate_tracks: track_off [T+1], obs_image [N_obs], obs_uv [N_obs,2]')
+    Kt = _contig(torch.as_tensor(K, dtype=torch.float32, device=dev).reshape(-1, 9))
+    Rt = _contig(torch.as_tensor(R, dtype=torch.float64, device=dev).reshape(-1, 9))
+    tt = _contig(torch.as_tensor(t, dtype=torch.float64, device=dev).reshape(-1, 3))
+    n_images = int(Kt.shape[0])
+    if Rt.shape[0] != n_images or tt.shape[0] != n_images:
+        raise ValueError(f'triangulate_tracks: {n_images} K but {Rt.shape[0]} R and {tt.shape[0]} t')
+    toff, oimg, ouv = _contig(track_off.to(torch.int32)), _contig(obs_image.to(torch.int32)), _contig(obs_uv.to(torch.float32))
+    rows = max(T, 1)
+    X = torch.zeros(rows, 3, dtype=torch.float64, device=dev)
+    err2 = torch.zeros(rows, dtype=torch.float64, device=dev)
+    valid, conflict, nin, hyp, rounds = (torch.zeros(rows, dtype=torch.int32, device=dev) for _ in range(5))
+    inl = torch.zeros(max(n_obs, 1), dtype=torch.uint8, device=dev)
+    L_ = _lib.lib()
+    ws = _ws.get('triangulate', L_.gf_triangulate_workspace_bytes(T, n_images), dev)
+    cos_min = math.cos(math.radians(float(min_angle_deg)))
+    check(L_.gf_triangulate(_p(toff), T, n_obs, _p(oimg), _p(ouv), _p(Kt), _p(Rt), _p(tt), n_images, float(pixel_thr), cos_min, int(min_obs),
+                            int(refit), int(seed), _p(X), _p(valid), _p(conflict), _p(nin), _p(hyp), _p(rounds), _p(err2), _p(inl), _p(ws),
+                            ws.numel(), _stream()), 'gf_triangulate')
+    return {'X': X[:T], 'valid': valid[:T], 'conflict': conflict[:T], 'n_inliers': nin[:T], 'hypothesis': hyp[:T], 'rounds': rounds[:T],
+            'err2': err2[:T], 'inliers': inl[:n_obs]}

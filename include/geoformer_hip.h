@@ -40,7 +40,7 @@ typedef enum { GF_F32 = 0, GF_F16 = 1, GF_BF16 = 2 } gf_dtype;
 /* Still 4 with gf_pos_encode_ptrs / gf_fine_gather_ptrs and gf_pos_encode_ragged / gf_fine_gather_ragged (with gf_map_record): entries appended at
  * the end change no existing one; a binding that needs them fails at load on the missing symbol (geoformer_amd/_lib.py binds every name).
  * Likewise with the gf_keypoint_* entries, gf_fundamental_* (gf_fundamental_ransac_lo and its workspace query included), gf_linear_rows,
- * gf_index_rows, gf_fine_rows*, gf_abspose_* and gf_xyz_lookup (with gf_xyz_map). */
+ * gf_index_rows, gf_fine_rows*, gf_abspose_* and gf_xyz_lookup (with gf_xyz_map), gf_track_link, gf_track_flatten and gf_triangulate*. */
 #define GF_ABI_VERSION 4
 int gf_abi_version(void);
 const char* gf_last_error(void);
@@ -805,6 +805,43 @@ int gf_abspose_ransac(const float* p2d, const float* p3d, const float* scores, c
                       void* stream);
 int gf_xyz_lookup(const gf_xyz_map* table, int P, const int32_t* pair_offsets, const float* pts, long pts_stride, int M, float* xyz,
                   void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Triangulating database tracks from known poses (the step localize_sfm_helper.py:reconstruct_database_pairs leaves to hloc's
+ * triangulation and COLMAP's point_triangulator; the reference has no code for it).  COLMAP parity is unpinned; the algorithm is the one
+ * stated in geoformer_amd/csrc/tri_solver.h (tracks = connected components of the keypoint match graph, two-view midpoint hypotheses,
+ * reprojection inliers in pixels, an optional Gauss-Newton refit on the inliers), which also compiles for the host
+ * (csrc/host/tri_host.cpp): bit-exact against that build.
+ *   gf_track_link
+ *     ids int32 [E,2] (per-image keypoint indices of every match row), id_off int32 [P + 1] (the rows of pair p), pair_images int32 [P,2],
+ *     kp_off int32 [n_images + 1] (node of keypoint k of image i = kp_off[i] + k; last = n_nodes) - all in DEVICE memory.
+ *     parent int32 [n_nodes] is set to the identity, then every row links its two nodes (lock-free union-find: compare-and-swap of the
+ *     larger root onto the smaller).  Afterwards every component is one tree whose root is its smallest node.  status int32 [1]: bit 0
+ *     (1) when a row named an image outside [0, n_images) or a keypoint its image does not have - such a row is skipped.
+ *   gf_track_flatten
+ *     parent[v] = the root of v for every node.  The partition and the roots do not depend on the order of execution.
+ *   gf_triangulate
+ *     track_off int32 [T + 1] in DEVICE memory (ascending, first 0, last n_obs: the observations of track k; entries are clamped into
+ *     [0, n_obs] before use), obs_image int32 [n_obs] (ascending inside a track), obs_uv fp32 [n_obs,2] pixels, K fp32 [n_images,9],
+ *     R fp64 [n_images,9], t fp64 [n_images,3] with x_cam = R X + t (an image without a pose: NaN - its observations take no part).
+ *     pixel_thr > 0; cos_min_angle: the cosine of the smallest triangulation angle of a hypothesis pair; min_obs >= 2; refit 0 .. 8
+ *     (0: the two-view midpoint winner and nothing else; R > 0: up to R refits on the inliers, three Gauss-Newton steps each, the
+ *     candidate taken iff it has at least as many inliers); T * 64 < 2^31; anything else is GF_ERR_INVALID_ARGUMENT.  A track of effective
+ *     length L has min(L (L - 1) / 2, 64) hypotheses: every pair up to L = 11, draws from (seed, track, t) above.
+ *     outputs: X fp64 [T,3] (zeros when not valid), valid int32 [T], conflict int32 [T] (an image occurs twice: not triangulated),
+ *     n_inliers int32 [T], hypothesis int32 [T] (the seeding pair; -1), rounds int32 [T] (refits accepted; 0: the midpoint's bits),
+ *     err2 fp64 [T] (mean squared reprojection error of the inliers), inliers uint8 [n_obs] (0 for every observation of a track that
+ *     is not valid).  T = 0 is a no-op.
+ *     workspace: gf_triangulate_workspace_bytes(T, n_images) bytes.  No host synchronisation, bit-identical from run to run.
+ * ------------------------------------------------------------------------------------------ */
+int gf_track_link(const int32_t* ids, const int32_t* id_off, const int32_t* pair_images, int P, int E, const int32_t* kp_off, int n_images,
+                  int n_nodes, int32_t* parent, int32_t* status, void* stream);
+int gf_track_flatten(int32_t* parent, int n_nodes, void* stream);
+size_t gf_triangulate_workspace_bytes(int T, int n_images);
+int gf_triangulate(const int32_t* track_off, int T, int n_obs, const int32_t* obs_image, const float* obs_uv, const float* K,
+                   const double* R, const double* t, int n_images, float pixel_thr, double cos_min_angle, int min_obs, int refit,
+                   uint32_t seed, double* X, int32_t* valid, int32_t* conflict, int32_t* n_inliers, int32_t* hypothesis, int32_t* rounds,
+                   double* err2, uint8_t* inliers, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
