@@ -33,6 +33,14 @@ int gf_fund_host_pencil(const double* F1, const double* F2, double* F_out) {
     return n;
 }
 
+// gs_offsets_range of solver_common.h, the clamp the kernels apply to a device-side offsets array: problem n of a list of M rows -> out [2]
+// (first row, number of rows)
+void gf_fund_host_offsets_range(const int32_t* offsets, int n, int M, int32_t* out) {
+    int off, len;
+    gs_offsets_range(offsets, n, M, off, len);
+    out[0] = off; out[1] = len;
+}
+
 // One refit (steps 2 - 5 of a round of fund_solver.h) from a given inlier set: matches [n][4], every row taken as a surviving row,
 // mask [n], norm [6] -> F_out [9] in pixels.  Returns 1, or 0 when the round fails.
 int gf_fund_host_refit_once(const float* matches, int n, const uint8_t* mask, const double* norm, double* F_out) {

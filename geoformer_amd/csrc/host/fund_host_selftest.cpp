@@ -10,6 +10,7 @@
 
 extern "C" int gf_fund_host_seven_point(const double* x0, const double* x1, const double* norm, double* F_out);
 extern "C" int gf_fund_host_pencil(const double* F1, const double* F2, double* F_out);
+extern "C" void gf_fund_host_offsets_range(const int32_t* offsets, int n, int M, int32_t* out);
 extern "C" int gf_fund_host_ransac(const float* matches, const float* scores, int n, float sc_thres, double pixel_thr, int iters, uint32_t seed,
                                    uint32_t sample, double* F_out, int32_t* hyp_out, int32_t* n_inliers, uint8_t* mask);
 extern "C" int gf_fund_host_ransac_lo(const float* matches, const float* scores, int n, float sc_thres, double pixel_thr, int iters, uint32_t seed,
@@ -222,6 +223,26 @@ int main() {
         std::vector<uint8_t> mask(n);
         CHECK(gf_fund_host_ransac_lo(m.data(), nullptr, n, 0.25f, 1.0, 64, 11, 0, 9, F, hyp, &nin, mask.data(), &rounds) == -1, "refit_rounds 9");
         CHECK(gf_fund_host_ransac_lo(m.data(), nullptr, n, 0.25f, 1.0, 64, 11, 0, -1, F, hyp, &nin, mask.data(), &rounds) == -1, "refit_rounds -1");
+    }
+    // ---- the offsets clamp, M = 200: o = clamp(offsets[n], 0, M), e = clamp(max(offsets[n + 1], o), 0, M)
+    {
+        const int M = 200;
+        const int32_t cases[][4] = {{0, 0, 0, 0},       {0, 7, 0, 7},     {7, 64, 7, 57},   {199, 200, 199, 1},          // in range, ascending
+                                    {-5, 30, 0, 30},    {-9, 0, 0, 0},    {INT32_MIN, 200, 0, 200},                      // a negative start
+                                    {150, 201, 150, 50}, {0, INT32_MAX, 0, 200},                                         // an end past M
+                                    {120, 40, 120, 0},  {200, 0, 200, 0}, {50, -3, 50, 0},                               // a descending pair
+                                    {201, 300, 200, 0}, {300, 201, 200, 0}, {INT32_MAX, INT32_MAX, 200, 0}};             // both past M
+        for (const auto& c : cases) {
+            const int32_t offs[3] = {-77, c[0], c[1]};
+            int32_t out[2] = {-1, -1};
+            gf_fund_host_offsets_range(offs, 1, M, out);
+            const int o = c[0] < 0 ? 0 : c[0] > M ? M : c[0];
+            int e = c[1] < o ? o : c[1];
+            e = e > M ? M : e;
+            CHECK(out[0] == c[2] && out[1] == c[3] && out[0] == o && out[1] == e - o, "offsets (%d, %d): (%d, %d), expected (%d, %d)", c[0], c[1],
+                  out[0], out[1], c[2], c[3]);
+        }
+        printf("offsets clamp: %d cases\n", (int)(sizeof(cases) / sizeof(cases[0])));
     }
     printf(g_fail ? "%d check(s) FAILED\n" : "all checks passed\n", g_fail);
     return g_fail ? 1 : 0;

@@ -101,14 +101,6 @@ struct TriArgs {
     uint8_t* inliers;
 };
 
-// the track's slice of the observations (offsets come from device memory: clamped into the buffers)
-__device__ __forceinline__ void tri_range(const TriArgs& a, int k, long& b, long& e) {
-    int o = a.track_off[k], n = a.track_off[k + 1];
-    o = min(max(o, 0), a.n_obs);
-    n = min(max(n, o), a.n_obs);
-    b = o; e = n;
-}
-
 __global__ __launch_bounds__(256) void tri_cams(TriArgs a) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= a.v.n_images) return;
@@ -125,10 +117,9 @@ __global__ __launch_bounds__(256) void tri_prepare(TriArgs a) {
     const int tid = threadIdx.x, k = blockIdx.x * 256 + tid;
     int H = 0;
     if (k < a.T) {
-        long b, e;
-        tri_range(a, k, b, e);
-        int L, conflict;
-        tr_track_scan(a.v, b, e, L, conflict);
+        int off, len, L, conflict;
+        gs_offsets_range(a.track_off, k, a.n_obs, off, len);         // (offsets come from device memory: clamped into the buffers)
+        tr_track_scan(a.v, off, off + len, L, conflict);
         H = conflict ? 0 : tr_hyp_count(L);
         a.leff[k] = L;
         a.conflict[k] = conflict;
@@ -189,9 +180,9 @@ __global__ __launch_bounds__(256) void tri_hypotheses(TriArgs a) {
     }
     const int k = klo, t = r - a.slot_loc[k];
     if (t < 0 || t >= a.nhyp[k]) return;                               // (cannot happen for consistent scans)
-    long b, e;
-    tri_range(a, k, b, e);
-    const int c = tr_hypothesis(a.v, (uint32_t)k, b, e, a.leff[k], t);
+    int off, len;
+    gs_offsets_range(a.track_off, k, a.n_obs, off, len);
+    const int c = tr_hypothesis(a.v, (uint32_t)k, off, off + len, a.leff[k], t);
     if (c >= 0) atomicMax(a.best + k, rt_key(c, t));
 }
 
@@ -199,9 +190,9 @@ __global__ __launch_bounds__(256) void tri_finish(TriArgs a) {
     __shared__ double ws[TR_GN_WS_DOUBLES * 256];
     const int tid = threadIdx.x, k = blockIdx.x * 256 + tid;
     if (k >= a.T) return;
-    long b, e;
-    tri_range(a, k, b, e);
-    tr_track_finish(a.v, (uint32_t)k, b, e, a.leff[k], a.conflict[k], rt_key_hyp(a.best[k]), GsWs{ws + tid, 256}, a.X + 3 * (size_t)k,
+    int off, len;
+    gs_offsets_range(a.track_off, k, a.n_obs, off, len);
+    tr_track_finish(a.v, (uint32_t)k, off, off + len, a.leff[k], a.conflict[k], rt_key_hyp(a.best[k]), GsWs{ws + tid, 256}, a.X + 3 * (size_t)k,
                     a.valid + k, a.n_inliers + k, a.hypothesis + k, a.rounds + k, a.err2 + k, a.inliers);
 }
 

@@ -20,6 +20,7 @@
 //                      (p, q) order, a rotation whose off-diagonal entry is exactly 0 skipped, t = sign(theta) / (|theta| + sqrt(theta^2 + 1)).
 //                      No convergence test: nothing that could differ between two builds decides how much work is done.
 //   gs_min_diag<N>     the index of the smallest diagonal entry (the smallest eigenvalue after gs_jacobi_sym); ties go to the lower index.
+//   gs_offsets_range   problem n's slice of a list of M rows addressed by an offsets array [N + 1], clamped into the list.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -47,6 +48,16 @@ struct GsWs {
     int s;
     GS_HD_MEMBER double& operator()(int i) const { return p[(long)i * s]; }
 };
+
+// offsets come from device memory, so nothing read from them is trusted: off = clamp(offsets[n], 0, M) and the slice ends at
+// clamp(max(offsets[n + 1], off), 0, M) - a descending pair is an empty slice, and nothing indexed with (off, len) leaves [0, M)
+GS_HD void gs_offsets_range(const int32_t* offsets, int n, int M, int& off, int& len) {
+    int o = offsets[n], e = offsets[n + 1];
+    o = o < 0 ? 0 : o; o = o > M ? M : o;
+    e = e < o ? o : e; e = e > M ? M : e;
+    off = o;
+    len = e - o;
+}
 
 GS_HD double gs_abs_or_inf(double v) {            // |v|, a NaN counted as +inf: it wins every pivot search and fails the solve
     const double a = fabs(v);

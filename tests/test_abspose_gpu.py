@@ -113,6 +113,38 @@ def test_refit_equals_host_build(noisy_problems, refit):
         assert err[1] < err[0], (n, err)
 
 
+@pytest.mark.parametrize('refit', [1, 4])
+def test_refit_equals_host_build_with_filtered_rows(noisy_problems, refit):
+    """the refit reads its first set from the mask and writes its last one back THROUGH the list of surviving rows: the first problem gets
+    rows that take no part - low scores in the middle of waves and on both sides of row 255 / 256, a NaN score, a NaN pixel, an inf point -
+    so that surviving row i is not row i.  The comparison is worth something only when a refit of that problem is accepted and moves rows in
+    and out of the set: the host build alone says that it does (at 1 px; at the 2 px of the other tests the accepted refit keeps the set)."""
+    scenes, p2d, p3d, offsets = noisy_problems
+    p2d, p3d = p2d.copy(), p3d.copy()
+    scores = np.random.default_rng(60).uniform(0.3, 1.0, len(p2d)).astype(np.float32)
+    scores[[3, 30, 31, 100, 130, 200, 255, 256, 299]] = 0.1
+    scores[150] = np.nan
+    p2d[17, 0] = np.nan; p3d[70, 2] = np.inf
+    keep = (scores >= 0.25) & np.isfinite(p2d).all(1) & np.isfinite(p3d).all(1)
+    assert keep[:300].sum() == 300 - 12 and keep[300:].all()
+    plain, host = (C.host_ransac(p2d[:300], p3d[:300], scores[:300], sample=0, iters=128, refit=r, thr=1.0) for r in (0, refit))
+    changed = np.flatnonzero(plain['inliers'] != host['inliers'])
+    assert host['rounds'] >= 1 and changed.min() < 255 and changed.max() > 256
+    dev = device(p2d, p3d, offsets, scores, thr=1.0, iters=128, refit=refit)
+    assert_equals_host(dev, p2d, p3d, offsets, scores, thr=1.0, iters=128, refit=refit)
+    assert dev['rounds'][0] >= 1 and not dev['inliers'][~keep].any()
+    assert (dev['n_inliers'] == [int(dev['inliers'][offsets[n]:offsets[n + 1]].sum()) for n in range(len(offsets) - 1)]).all()
+
+
+def test_refit_of_problems_that_cannot_be_refitted_equals_host_build(nine_problems):
+    """the refit stage launched over empty problems, problems below the minimum and a minimal one: rounds 0 and the P3P winner's bits where
+    nothing is refitted, against the host build"""
+    scenes, p2d, p3d, offsets = nine_problems
+    dev = device(p2d, p3d, offsets, refit=4)
+    assert_equals_host(dev, p2d, p3d, offsets, refit=4)
+    assert not dev['rounds'][:3].any() and list(dev['valid'][:3]) == [0, 0, 1]
+
+
 def test_refit_zero_is_the_plain_entry(noisy_problems):
     scenes, p2d, p3d, offsets = noisy_problems
     a, b = device(p2d, p3d, offsets, iters=128, refit=0), device(p2d, p3d, offsets, iters=128)

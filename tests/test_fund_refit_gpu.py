@@ -1,4 +1,4 @@
-"""The refit of the fundamental matrix on its inliers on the GPU: gf_fundamental_ransac_lo (fund_refit of csrc/k_fundamental.hip behind
+"""The refit of the fundamental matrix on its inliers on the GPU: gf_fundamental_ransac_lo (rt_refit<FundModel> of csrc/k_fundamental.hip behind
 ops.ransac_fundamental(refit=R)) against the host build of the same fund_solver.h, bit for bit, then matcher.verify_matches(refit=R),
 consolidate_matches(keep=...) and `pairs --verify --verify-refit`.  Scenes: tests/fund_refit_cases.py."""
 import os
@@ -141,6 +141,20 @@ def test_zero_rounds_is_gf_fundamental_ransac(pairs11, host_runs):
         assert np.array_equal(lo8['F'][n].view(np.int64), plain['F'][n].view(np.int64)) and lo8['n_inliers'][n] == plain['n_inliers'][n]
         assert np.array_equal(lo8['inliers'][offsets[n]:offsets[n + 1]], plain['inliers'][offsets[n]:offsets[n + 1]])
     assert np.array_equal(lo8['hypothesis'], plain['hypothesis']) and (lo8['n_inliers'] >= plain['n_inliers']).all()
+
+
+def test_refit_of_pairs_that_cannot_be_refitted_equals_host_build():
+    """the refit stage launched over the pairs of tests/test_fundamental_gpu.py - an empty pair, one below the minimum, a minimal one (seven
+    inliers: not refitted), 63 .. 300 rows - through gf_fundamental_ransac_lo itself: rounds 0 and the seven-point winner's bits where
+    nothing is refitted, against the host build"""
+    sizes = (0, 6, 7, 63, 64, 65, 129, 300)
+    m = np.concatenate([C.scene(200 + i, n, 0.3 if n >= 63 else 0.0)['m'] for i, n in enumerate(sizes)])
+    offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+    scores = np.ones(len(m), np.float32)
+    rc, dev = device_lo(m, scores, offsets, 4)
+    assert rc == 0
+    assert_equals_host(dev, host(m, scores, offsets, 4), offsets)
+    assert list(dev['valid']) == [0, 0, 1, 1, 1, 1, 1, 1] and not dev['rounds'][:3].any() and dev['n_inliers'][2] == 7
 
 
 def test_two_calls_give_the_same_bits(pairs11):

@@ -191,3 +191,42 @@ def test_deterministic_and_keyed_by_seed_and_pair_index():
 def test_bad_iteration_count_is_an_invalid_argument(iters):
     sc = C.scene(123, 50, 0.3)
     assert C.host_ransac(sc['m'], iters=iters)['status'] == -1       # GF_ERR_INVALID_ARGUMENT
+
+
+# ------------------------------------------------------------------------------------------------------------ the offsets clamp
+def host_offsets_range(offsets, n, M):
+    import ctypes
+    off = np.ascontiguousarray(offsets, np.int32)
+    out = np.full(2, -7, np.int32)
+    f = C.host_lib().gf_fund_host_offsets_range
+    f.restype, f.argtypes = None, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+    f(off.ctypes.data, n, M, out.ctypes.data)
+    return int(out[0]), int(out[1])
+
+
+def test_offsets_clamp():
+    """gs_offsets_range of solver_common.h, which every stage that reads a device-side offsets array applies (fundamental matrix, absolute
+    pose, triangulation), through the host build: o = clamp(offsets[n], 0, M), e = clamp(max(offsets[n + 1], o), 0, M) -> (o, e - o).
+    Out-of-range offsets are tested here and only here: on the device they would be indexed with."""
+    M = 200
+
+    def rule(a, b):
+        o = min(max(a, 0), M)
+        e = min(max(max(b, o), 0), M)
+        return o, e - o
+
+    offsets = [0, 0, 7, 64, 199, 200]                                  # in range, ascending (an empty and a one-row slice among them)
+    for n in range(len(offsets) - 1):
+        assert host_offsets_range(offsets, n, M) == rule(offsets[n], offsets[n + 1]) == (offsets[n], offsets[n + 1] - offsets[n])
+    for a, b in ((-5, 30), (-2 ** 31, 200), (-1, -1), (-9, 0)):        # a negative start
+        assert host_offsets_range([a, b], 0, M) == rule(a, b)
+    assert host_offsets_range([-5, 30], 0, M) == (0, 30)
+    for a, b in ((150, 201), (0, 2 ** 31 - 1), (199, 1000)):           # an end past M
+        assert host_offsets_range([a, b], 0, M) == rule(a, b)
+    assert host_offsets_range([150, 201], 0, M) == (150, 50)
+    for a, b in ((120, 40), (200, 0), (1, 0), (50, -3)):               # a descending pair: empty, at the clamped start
+        assert host_offsets_range([a, b], 0, M) == rule(a, b) == (a, 0)
+    for a, b in ((201, 300), (300, 201), (2 ** 31 - 1, 2 ** 31 - 1)):  # both past M
+        assert host_offsets_range([a, b], 0, M) == rule(a, b) == (M, 0)
+    assert host_offsets_range([9, 9, 120, 40, 77], 2, M) == (120, 0)   # entry n of a longer array
+    assert host_offsets_range([3, 5], 0, 0) == (0, 0)                  # an empty list

@@ -130,7 +130,7 @@ def main(argv=None):
             out[k].append(fn())
     log(f'{WINDOWS} windows per form, the forms alternating; one window = one pass over the {Q} queries')
     log(line('(a) localize_queries end to end, no events', out['loc0'], 'ms'))
-    log(line('(b) abs_prepare + rt_score<AbsModel> + abs_final (device events)', kern['abs0'], 'ms'))
+    log(line('(b) rt_prepare, rt_score, rt_final <AbsModel> (device events)', kern['abs0'], 'ms'))
     log(line(f'(c) localize_queries(refit={REFIT}) end to end, no events', out['loc4'], 'ms'))
     log(line(f'(d) the four kernels, refit={REFIT} (device events)', kern['abs4'], 'ms'))
     log(line(f'(e) gf_fundamental_ransac, same row counts, {iters} hypotheses: three kernels', kern['fund'], 'ms'))

@@ -203,7 +203,7 @@ def main(argv=None):
     log(f'{WINDOWS} windows per form, the forms alternating; one window = one pass over the {len(pairs)} pairs')
     log(line('(a) verify_matches end to end, kernels under events', out['verify'], 'ms'))
     log(line('(a) verify_matches end to end, no events', out['verify_plain'], 'ms'))
-    log(line('(b) fund_prepare + rt_score<FundModel> + fund_final (device events)', kern_ms, 'ms'))
+    log(line('(b) rt_prepare, rt_score, rt_final <FundModel> (device events)', kern_ms, 'ms'))
     log(line(f'(c) gf_pose_essential_ransac, same rows, {iters} hypotheses (device events)', out['pose'], 'ms'))
     log(line('(d) consolidate_matches end to end', out['consolidate'], 'ms'))
     log(line('(e) extract_features + match_features, the 120 pairs', out['match'], 'ms'))
