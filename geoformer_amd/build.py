@@ -26,6 +26,7 @@ KEYPOINT_HOST_LIB = os.path.join(OBJ, 'libkeypoint_host.so')
 FUND_HOST_LIB = os.path.join(OBJ, 'libfund_host.so')
 ABSPOSE_HOST_LIB = os.path.join(OBJ, 'libabspose_host.so')
 TRI_HOST_LIB = os.path.join(OBJ, 'libtri_host.so')
+COVIS_HOST_LIB = os.path.join(OBJ, 'libcovis_host.so')
 
 
 def _headers_digest():
@@ -122,6 +123,14 @@ def build_tri_host(verbose=True):
                                                                  'keypoint_spec.h', 'gf_hash.h')), verbose)
 
 
+def build_covis_host(verbose=True):
+    """TEST INFRASTRUCTURE and CPU reference: the serial host form of the covisibility clustering and the 2-D - 3-D rows of sparse
+    localisation (csrc/host/covis_host.cpp over csrc/covis_spec.h, the text k_covis.hip compiles for the device).  Only tests and
+    tools/covis_probe.py load it."""
+    return _build_host_lib(COVIS_HOST_LIB, 'covis_host.stamp', os.path.join(CSRC, 'host', 'covis_host.cpp'),
+                           (os.path.join(CSRC, 'covis_spec.h'),), verbose)
+
+
 def build(verbose=True, jobs=4):
     os.makedirs(OBJ, exist_ok=True)
     build_pose_host(verbose)
@@ -130,6 +139,7 @@ def build(verbose=True, jobs=4):
     build_fund_host(verbose)
     build_abspose_host(verbose)
     build_tri_host(verbose)
+    build_covis_host(verbose)
     srcs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.hip'))
     hdig = _headers_digest()
     with ThreadPoolExecutor(jobs) as ex:

@@ -577,6 +577,12 @@ class LocalizedQueries(NamedTuple):
     localized: np.ndarray    # [Q] bool: a model was found and it has at least min_inliers inliers
     masks: list              # per PAIR: [n_p] bool, the inliers of a localised query's pair; all False otherwise
     rounds: np.ndarray       # [Q] int32: refits on the inliers accepted per query (zeros without refit)
+    # localize_queries_sparse with covis_cluster or dedup (None otherwise):
+    n_clusters: Optional[np.ndarray] = None   # [Q] int32: covisibility clusters of the query's database images (1 with clustering off, 0: no image)
+    cluster: Optional[np.ndarray] = None      # [Q] int32: the number of the winning cluster, -1 if there is none
+    db_names: Optional[list] = None           # per query: its database images, in order of first appearance in the pair list
+    db_cluster: Optional[list] = None         # per query: int32 array, the cluster of each entry of db_names
+    cluster_inliers: Optional[list] = None    # per query: int32 [C_q], the inliers of each cluster's pose (0: RANSAC found no model)
 
 
 def localize_queries(pairs, results, intrinsics, xyz_maps, thr=12.0, min_inliers=12, sc_thres=0.25, iters=None, device='cuda', refit=0):
@@ -842,18 +848,27 @@ def _assemble_tracks(n, kp_off, T, X, err2, valid, conflict, toff, oimg, okp, in
 
 
 def localize_queries_sparse(cm: ConsolidatedMatches, tt: TriangulatedTracks, queries, intrinsics, thr=12.0, min_inliers=12, iters=None, refit=0,
-                            device='cuda') -> LocalizedQueries:
+                            device='cuda', covis_cluster=False, dedup=False) -> LocalizedQueries:
     """Camera poses of query images against triangulated points: the sparse counterpart of localize_queries for datasets with database
     poses and no depth.  queries: image names of cm.  For every pair of cm that joins a query and an image with points (the query on either
     side), the rows are p2d = the query's keypoints, p3d = the point of the other image's keypoint (tt.point_of_keypoint; NaN where it has
     none, such a row takes no part).  All pairs of a query form one problem in pair order, then ops.ransac_absolute_pose as in
     localize_queries.  intrinsics[query]: 3 x 3 K.  masks: one per pair of cm ([n_p] bool; all False for a pair that joins no query to
-    points).  Indexing on the host and an existing op: no new kernel."""
+    points).  With both flags off: indexing on the host and an existing op.
+    covis_cluster (hloc's covisibility_clustering): the database images of a query are split into the connected components of the
+    covisibility graph restricted to them (two images are linked iff they share a point of tt), one pose per component, and the component
+    with the most inliers wins (then the lowest cluster number) - retrieval that returns two places that look alike no longer pools them.
+    dedup: every (query keypoint, point) counts once per problem, however many database images show it; the mask of a repeated row is
+    its first occurrence's.  With either flag the rows are built on the device (ops.covis_clusters, ops.sparse_rows, ops.select_cluster;
+    the rule is csrc/covis_spec.h; one upload, pair-level bookkeeping on the host) and the result carries n_clusters, cluster, db_names,
+    db_cluster and cluster_inliers.  At most 1024 database images per query."""
     names = list(dict.fromkeys(queries))
     Q = len(names)
     missing = [q for q in names if q not in intrinsics or q not in cm.names]
     if missing:
         raise ValueError(f'localize_queries_sparse: no intrinsics for, or no image named {missing[0]!r}')
+    if covis_cluster or dedup:
+        return _localize_sparse_device(cm, tt, names, intrinsics, thr, min_inliers, iters, refit, device, bool(covis_cluster), bool(dedup))
     p2d, p3d, query_off, pair_off, used, owner = _sparse_rows(cm, tt, names)
     masks = [np.zeros(len(m), bool) for m in cm.matches]
     M = len(p2d)
@@ -906,6 +921,129 @@ def _sparse_rows(cm, tt, names):
     p2d = np.concatenate([rows2[k] for k in order]) if order else np.zeros((0, 2), np.float32)
     p3d = np.concatenate([rows3[k] for k in order]) if order else np.zeros((0, 3), np.float32)
     return p2d, p3d, query_off, pair_off, [used[k] for k in order], [owner[k] for k in order]
+
+
+def _covis_tables(cm, tt, names):
+    """The pair-level bookkeeping of the device path (csrc/covis_spec.h, step 1; O(pairs), after one count of tt.obs_image per image for
+    "has a point"): which pairs contribute (the rule of _sparse_rows), every query's database list in order of first appearance, and each
+    list sorted by image id.  -> dict(pairs int32 [C,8], pair_row_off
+    int32 [C+1], used: the index in cm of each contributing pair, list_off int32 [Q+1], list_img, sorted_img, sorted_pos int32 [L])."""
+    qidx = {q: k for k, q in enumerate(names)}
+    image_q = [qidx.get(nm, -1) for nm in cm.names]
+    has_pts = np.bincount(np.asarray(tt.obs_image, np.int64), minlength=len(cm.names)) > 0       # an image with a point has an observation
+    id_off = np.concatenate([[0], np.cumsum([len(m) for m in cm.matches])]).astype(np.int64)
+    if id_off[-1] >= 2 ** 31:
+        raise ValueError('localize_queries_sparse: 2^31 match rows or more')
+    lists, where, pairs, used = [[] for _ in names], [{} for _ in names], [], []
+    for p in range(len(cm.matches)):
+        i, j = (int(v) for v in cm.pair_images[p])
+        for qs, ds, col in ((i, j, 0), (j, i, 1)):
+            if image_q[qs] >= 0 and image_q[ds] < 0 and has_pts[ds]:
+                q = image_q[qs]
+                pos = where[q].setdefault(ds, len(lists[q]))
+                if pos == len(lists[q]):
+                    lists[q].append(ds)
+                pairs.append((q, qs, ds, id_off[p], id_off[p + 1], col, pos, 0)), used.append(p)
+                break
+    longest = max([len(x) for x in lists], default=0)
+    if longest > ops.CV_MAX_LIST:
+        raise ValueError(f'localize_queries_sparse: a query with {longest} database images; at most {ops.CV_MAX_LIST}')
+    pairs = np.array(pairs, np.int32).reshape(-1, ops.CV_PAIR_WORDS)
+    flat = lambda xs: np.array([v for x in xs for v in x], np.int32)              # noqa: E731
+    by_id = [sorted(range(len(x)), key=x.__getitem__) for x in lists]
+    return {'pairs': pairs, 'pair_row_off': np.concatenate([[0], np.cumsum(pairs[:, 4].astype(np.int64) - pairs[:, 3])]).astype(np.int32),
+            'used': used, 'list_off': np.concatenate([[0], np.cumsum([len(x) for x in lists])]).astype(np.int32), 'list_img': flat(lists),
+            'sorted_img': flat([[x[a] for a in o] for x, o in zip(lists, by_id)]), 'sorted_pos': flat(by_id)}
+
+
+def _device_rows(cm, tt, names, intrinsics, tb, device, covis_cluster, dedup):
+    """The device row path of localize_queries_sparse for the tables tb of _covis_tables: one upload, ops.covis_clusters, ops.sparse_rows
+    (one read of the sizes) -> (K fp32 [Q,9], cluster, n_clusters, the dict of ops.sparse_rows with p2d and p3d), all on the device."""
+    Q, C = len(names), len(tb['pairs'])
+    kp_off = np.concatenate([[0], np.cumsum([len(k) for k in cm.keypoints])]).astype(np.int32)
+    n_nodes, T = int(kp_off[-1]), len(tt.points)
+    ids = np.concatenate([np.asarray(m, np.int32).reshape(-1, 2) for m in cm.matches])
+    E = len(ids)
+    Ks = np.stack([np.asarray(intrinsics[q], dtype=np.float32).reshape(9) for q in names])
+    kps = np.concatenate([np.asarray(k, np.float32).reshape(-1, 2) for k in cm.keypoints])
+    parts = (kp_off, np.concatenate(tt.point_of_keypoint).astype(np.int32), np.asarray(tt.obs_offsets, np.int32), np.asarray(tt.obs_image, np.int32),
+             tb['pairs'], tb['pair_row_off'], ids, tb['list_off'], tb['list_img'], tb['sorted_img'], tb['sorted_pos'], Ks, kps,
+             np.asarray(tt.points).astype(np.float32))                 # the points rounded once to fp32, as _sparse_rows does
+    block = np.concatenate([np.ascontiguousarray(a).reshape(-1).view(np.int32) for a in parts])
+    d = torch.from_numpy(block).to(device)                             # one upload
+    o = 0
+
+    def take(a, dtype=torch.int32, *shape):
+        nonlocal o
+        v = d[o:o + a.size].view(dtype)
+        o += a.size
+        return v.view(*shape) if shape else v
+    kpo, pok, ooff, oimg = (take(a) for a in parts[:4])
+    prs, pro, idd = take(parts[4], torch.int32, C, ops.CV_PAIR_WORDS), take(parts[5]), take(parts[6], torch.int32, E, 2)
+    loff, limg, simg, spos = (take(a) for a in parts[7:11])
+    Kd, kpd, ptd = take(Ks, torch.float32, Q, 9), take(kps, torch.float32, n_nodes, 2), take(parts[13], torch.float32, T, 3)
+    cluster, ncl, status = ops.covis_clusters(kpo, pok, ooff, oimg, loff, limg, simg, spos, tb, enable=covis_cluster)
+    rows = ops.sparse_rows(prs, pro, idd, kpo, pok, T, loff, cluster, ncl, tb, dedup=dedup, status=status, keypoints=kpd, points=ptd)
+    return Kd, cluster, ncl, rows
+
+
+def _localize_sparse_device(cm, tt, names, intrinsics, thr, min_inliers, iters, refit, device, covis_cluster, dedup):
+    """localize_queries_sparse with covis_cluster or dedup: one upload, the cluster kernel, the row kernel with torch's sorts behind it, one
+    read of the sizes, ops.ransac_absolute_pose over the problems, the selection kernel, one read back."""
+    Q = len(names)
+    tb = _covis_tables(cm, tt, names)
+    Lt, used = len(tb['list_img']), tb['used']
+    masks = [np.zeros(len(m), bool) for m in cm.matches]
+    db_names = [[cm.names[i] for i in tb['list_img'][tb['list_off'][q]:tb['list_off'][q + 1]]] for q in range(Q)]
+    zero = np.zeros(Q, np.int32)
+
+    def result(R, t, nin, localized, rounds, ncl, win, cluster, cin):
+        base = np.concatenate([[0], np.cumsum(ncl)])
+        return LocalizedQueries(names, R, t, nin, localized, masks, rounds, ncl, win,
+                                db_names, [cluster[tb['list_off'][q]:tb['list_off'][q + 1]].copy() for q in range(Q)],
+                                [cin[base[q]:base[q + 1]].copy() for q in range(Q)])
+    if Q == 0 or Lt == 0:                                              # no contributing pair: every list is empty, C_q = 0
+        return result(np.zeros((Q, 3, 3)), np.zeros((Q, 3)), zero, np.zeros(Q, bool), zero.copy(), zero.copy(), np.full(Q, -1, np.int32),
+                      np.zeros(0, np.int32), np.zeros(0, np.int32))
+    with torch.cuda.device(device):
+        Kd, cluster, ncl, rows = _device_rows(cm, tt, names, intrinsics, tb, device, covis_cluster, dedup)
+        N, M = rows['N'], rows['M']
+        if M == 0:
+            ncl_h, cl_h = ncl.cpu().numpy(), cluster.cpu().numpy()
+            return result(np.zeros((Q, 3, 3)), np.zeros((Q, 3)), zero, np.zeros(Q, bool), zero.copy(), ncl_h, np.full(Q, -1, np.int32), cl_h,
+                          np.zeros(N, np.int32))
+        query_of_prob = torch.repeat_interleave(torch.arange(Q, device=ncl.device), ncl.long(), output_size=N)
+        rs = ops.ransac_absolute_pose(rows['p2d'], rows['p3d'], None, rows['prob_off'], N, Kd[query_of_prob], pixel_thr=thr,
+                                      iters=ops.ABS_RANSAC_ITERS if iters is None else iters, refit=refit)
+        sel = ops.select_cluster(rows['prob_base'], rs, rows['row_prob'], rows['slot'], min_inliers)
+        out = torch.cat([x.reshape(-1).view(torch.uint8) for x in (sel['R'], sel['t'], sel['winner'], sel['localized'], sel['n_inliers'], sel['rounds'],
+                                                                   ncl, cluster, sel['cluster_inliers'], sel['mask'])]).cpu().numpy()
+    o = 0
+
+    def read(count, dtype, *shape):
+        nonlocal o
+        v = out[o:o + count * np.dtype(dtype).itemsize].view(dtype).copy()
+        o += count * np.dtype(dtype).itemsize
+        return v.reshape(*shape) if shape else v
+    R, t = read(9 * Q, np.float64, Q, 3, 3), read(3 * Q, np.float64, Q, 3)
+    win, localized, nin, rounds, ncl_h = read(Q, np.int32), read(Q, np.int32).astype(bool), read(Q, np.int32), read(Q, np.int32), read(Q, np.int32)
+    cl_h, cin, mask = read(Lt, np.int32), read(N, np.int32), out[o:].astype(bool)
+    for c, p in enumerate(used):                                       # (a pair listed with a query contributes once; the masks of a query
+        if localized[tb['pairs'][c, 0]]:                               #  that is not localised stay False, as with the flags off)
+            masks[p] = mask[tb['pair_row_off'][c]:tb['pair_row_off'][c + 1]].copy()
+    return result(R, t, nin, localized, rounds, ncl_h, win, cl_h, cin)
+
+
+def read_triangulated(path) -> TriangulatedTracks:
+    """What `triangulate --out FILE.npz` wrote -> TriangulatedTracks.  A file from before n_tracks, n_conflict and n_rejected were saved
+    reads with -1 for the three counts."""
+    with np.load(path) as z:
+        kp_off = np.asarray(z['kp_offsets'], np.int64)
+        pok = np.asarray(z['point_of_keypoint'], np.int32)
+        counts = [int(z[k]) if k in z.files else -1 for k in ('n_tracks', 'n_conflict', 'n_rejected')]
+        return TriangulatedTracks(np.asarray(z['points'], np.float64).reshape(-1, 3), np.asarray(z['errors'], np.float64),
+                                  np.asarray(z['obs_offsets'], np.int32), np.asarray(z['obs_image'], np.int32), np.asarray(z['obs_keypoint'], np.int32),
+                                  [pok[kp_off[i]:kp_off[i + 1]].copy() for i in range(len(kp_off) - 1)], *counts)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1075,6 +1213,7 @@ def eval_hpatches(matcher, data_root, ransac_thres=3, thres=(1, 3, 5, 10), scale
 #                                         [--verify [--verify-thr T] [--min-inliers K] [--verify-refit [R]]]   (two-view verification: fundamental-matrix RANSAC per pair)
 #   python -m geoformer_amd.matcher localize LIST --xyz DIR --intrinsics FILE [--out FILE] [--thr T] [--min-inliers K] [--refit [R]]   (hloc's localize_sfm / localize_inloc)
 #   python -m geoformer_amd.matcher triangulate KEYPOINTS_DIR --poses FILE --intrinsics FILE [--out FILE.npz] [--thr T] [--min-angle A] [--min-obs K] [--refit [R]]   (hloc's triangulation)
+#   python -m geoformer_amd.matcher localize-sparse KEYPOINTS_DIR --points FILE.npz --queries FILE --intrinsics FILE [--covis-cluster] [--dedup] [--thr T] [--min-inliers K] [--refit [R]] [--out FILE]   (hloc's localize_sfm)
 # ---------------------------------------------------------------------------------------------
 def build_parser():
     """Defaults follow the reference per sub-command: `match` = inference.py:107 (imsize 640, matches scaled back to the
@@ -1158,6 +1297,21 @@ def build_parser():
     tri.add_argument('--refit', type=int, nargs='?', const=4, default=2, metavar='R',
                      help='refit every point on its inliers up to R times (0 .. 8; the bare flag: 4; default 2) and select the inliers again')
     tri.add_argument('--device', default='cuda')
+    ls = sub.add_parser('localize-sparse', help='camera poses of query images against triangulated points, from the files of `pairs --keypoints` '
+                                                'and `triangulate --out` (no model)')
+    ls.add_argument('keypoints', metavar='KEYPOINTS_DIR', help='what `pairs --keypoints DIR` wrote, over database and query images')
+    ls.add_argument('--points', metavar='FILE.npz', required=True, help='what `triangulate --out` wrote for the same KEYPOINTS_DIR')
+    ls.add_argument('--queries', metavar='FILE', required=True, help='one query image name per line (as in names.txt, or relative to FILE)')
+    ls.add_argument('--intrinsics', metavar='FILE', required=True, help='one line per query: path fx fy cx cy')
+    ls.add_argument('--covis-cluster', action='store_true',
+                    help="split every query's database images into covisibility clusters, one pose per cluster, the one with the most inliers wins")
+    ls.add_argument('--dedup', action='store_true', help='count every (query keypoint, 3-D point) once per problem')
+    ls.add_argument('--thr', type=float, default=12.0, help='inlier threshold, reprojection error in pixels')
+    ls.add_argument('--min-inliers', type=int, default=12, help='a query with fewer inliers is not localised')
+    ls.add_argument('--refit', type=int, nargs='?', const=4, default=0, metavar='R',
+                    help='refit every pose on its inliers up to R times (1 .. 8; the bare flag: 4) and select the inliers again')
+    ls.add_argument('--out', default=None, help='file with one line per localised query: path qw qx qy qz tx ty tz (x_cam = R X + t)')
+    ls.add_argument('--device', default='cuda')
     for p in (h, q, loc):
         p.add_argument('--cache-gb', type=float, default=None,
                        help='byte budget of the feature store in GB: least recently used images are dropped and extracted again when '
@@ -1176,6 +1330,53 @@ def build_parser():
     return ap
 
 
+def write_triangulated(path, tt: TriangulatedTracks):
+    """What `triangulate --out` writes and read_triangulated reads: points, errors, obs_offsets, obs_image, obs_keypoint, point_of_keypoint
+    (all images, concatenated in the order of names.txt), kp_offsets, and the counts n_tracks, n_conflict, n_rejected."""
+    np.savez(path, points=tt.points, errors=tt.errors, obs_offsets=tt.obs_offsets, obs_image=tt.obs_image, obs_keypoint=tt.obs_keypoint,
+             point_of_keypoint=np.concatenate(tt.point_of_keypoint) if tt.point_of_keypoint else np.zeros(0, np.int32),
+             kp_offsets=np.concatenate([[0], np.cumsum([len(p) for p in tt.point_of_keypoint])]).astype(np.int32),
+             n_tracks=np.int32(tt.n_tracks), n_conflict=np.int32(tt.n_conflict), n_rejected=np.int32(tt.n_rejected))
+
+
+def run_localize_sparse(args):
+    """The `localize-sparse` sub-command: the last link of the chain from the files the other sub-commands write.  A relative name in the
+    queries and intrinsics files is looked up both as written and relative to its file, as run_triangulate does."""
+    cm = read_consolidated(args.keypoints)
+    tt = read_triangulated(args.points)
+    if len(tt.point_of_keypoint) != len(cm.names) or any(len(p) != len(k) for p, k in zip(tt.point_of_keypoint, cm.keypoints)):
+        raise SystemExit(f'localize-sparse: {args.points} was not written for the keypoints under {args.keypoints}')
+    intr = read_intrinsics(args.intrinsics)
+    base = os.path.dirname(os.path.abspath(args.intrinsics))
+    for name in cm.names:
+        full = name if os.path.isabs(name) else os.path.normpath(os.path.join(base, name))
+        if name not in intr and full in intr:
+            intr[name] = intr[full]
+    qbase = os.path.dirname(os.path.abspath(args.queries))
+    known = {(nm if os.path.isabs(nm) else os.path.normpath(os.path.join(qbase, nm))): nm for nm in cm.names}
+    queries = []
+    with open(args.queries) as f:
+        for line in f:
+            q = line.strip()
+            if not q or q.startswith('#'):
+                continue
+            full = q if os.path.isabs(q) else os.path.normpath(os.path.join(qbase, q))
+            queries.append(q if q in cm.names else known.get(full, q))
+    lq = localize_queries_sparse(cm, tt, queries, intr, args.thr, args.min_inliers, refit=args.refit, device=args.device,
+                                 covis_cluster=args.covis_cluster, dedup=args.dedup)
+    if args.out:
+        with open(args.out, 'w') as f:
+            for k, name in enumerate(lq.names):
+                if lq.localized[k]:
+                    f.write(' '.join([name] + [repr(float(v)) for v in (*rotation_to_quaternion(lq.R[k]), *lq.t[k])]) + '\n')
+    print(f'{int(lq.localized.sum())} of {len(lq.names)} queries localised against {len(tt.points)} points (thr {args.thr} px, at least '
+          f'{args.min_inliers} inliers' + (', covisibility clusters' if args.covis_cluster else '') + (', unique rows' if args.dedup else '') + ')'
+          + (f'; {int((lq.n_clusters > 1).sum())} queries with more than one cluster' if args.covis_cluster else '')
+          + (f'; the refit on the inliers (up to {args.refit} rounds) changed {int((lq.rounds > 0).sum())} queries' if args.refit else '')
+          + (f' -> {args.out}' if args.out else ''))
+    return lq
+
+
 def run_triangulate(args):
     """The `triangulate` sub-command: names.txt lists the images as the pair list named them, so a relative name in the poses and
     intrinsics files is looked up both as written and relative to its file."""
@@ -1189,9 +1390,7 @@ def run_triangulate(args):
                 table[name] = table[full]
     tt = triangulate(cm, intr, poses, args.thr, args.min_angle, args.min_obs, args.refit, device=args.device)
     if args.out:
-        np.savez(args.out, points=tt.points, errors=tt.errors, obs_offsets=tt.obs_offsets, obs_image=tt.obs_image, obs_keypoint=tt.obs_keypoint,
-                 point_of_keypoint=np.concatenate(tt.point_of_keypoint) if tt.point_of_keypoint else np.zeros(0, np.int32),
-                 kp_offsets=np.concatenate([[0], np.cumsum([len(p) for p in tt.point_of_keypoint])]).astype(np.int32))
+        write_triangulated(args.out, tt)
     print(f'{len(tt.points)} points from {tt.n_tracks} tracks of {sum(n in poses for n in cm.names)} posed images ({tt.n_conflict} with an image '
           f'twice, {tt.n_rejected} without a point; thr {args.thr} px, angle >= {args.min_angle} deg, at least {args.min_obs} observations, up '
           f'to {args.refit} refits); {len(tt.obs_image)} observations, median reprojection error '
@@ -1200,13 +1399,18 @@ def run_triangulate(args):
 
 
 def main(argv=None):
-    """`python -m geoformer_amd.matcher match|hpatches|pairs|localize|triangulate ...` (arguments: build_parser)."""
+    """`python -m geoformer_amd.matcher match|hpatches|pairs|localize|triangulate|localize-sparse ...` (arguments: build_parser)."""
     ap = build_parser()
     args = ap.parse_args(argv)
     if args.cmd == 'triangulate':                                       # no model: keypoints, matches and poses in, points out
         if args.min_obs < 2 or not 0 <= args.refit <= 8 or not args.thr > 0:
             ap.error('triangulate: need --min-obs >= 2, --refit 0 .. 8 and --thr > 0')
         run_triangulate(args)
+        return
+    if args.cmd == 'localize-sparse':                                   # no model either: keypoints, matches and points in, poses out
+        if not 0 <= args.refit <= 8 or not args.thr > 0:
+            ap.error('localize-sparse: need --refit 0 .. 8 and --thr > 0')
+        run_localize_sparse(args)
         return
     world = int(os.environ.get('WORLD_SIZE', '1'))
     local = int(os.environ.get('LOCAL_RANK', '0'))

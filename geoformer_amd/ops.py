@@ -1425,3 +1425,161 @@ def triangulate_tracks(track_off, obs_image, obs_uv, K, R, t, pixel_thr=4.0, min
                             ws.numel(), _stream()), 'gf_triangulate')
     return {'X': X[:T], 'valid': valid[:T], 'conflict': conflict[:T], 'n_inliers': nin[:T], 'hypothesis': hyp[:T], 'rounds': rounds[:T],
             'err2': err2[:T], 'inliers': inl[:n_obs]}
+
+
+# ---------------------------------------------------------------------------------------------
+# sparse localisation: covisibility clusters, unique 2-D - 3-D rows, the winning cluster (csrc/k_covis.hip over csrc/covis_spec.h)
+# ---------------------------------------------------------------------------------------------
+CV_MAX_LIST = 1024              # covis_spec.h: the longest database list of one query
+CV_PAIR_WORDS = 8
+_CV_FLAGS = ((1, 'an image that does not exist'), (2, 'a keypoint its image does not have, or a row outside ids'),
+             (4, 'a point that does not exist'), (8, 'a list position outside its list'))
+
+
+def _cv_raise(what, flags):
+    if flags:
+        raise _lib.GeoFormerHipError(f'{what}: the tables name ' + '; '.join(t for b, t in _CV_FLAGS if flags & b))
+
+
+def _host_i32(a):
+    """a small int32 table as a contiguous numpy array and its address (the *_host arguments: read before anything is enqueued)"""
+    import numpy as np
+    a = np.ascontiguousarray(a, dtype=np.int32)
+    return a, ctypes.c_void_p(a.ctypes.data)
+
+
+def _i32(t, dev):
+    return _contig(t.to(device=dev, dtype=torch.int32))
+
+
+def covis_clusters(kp_off, point_of_keypoint, obs_offsets, obs_image, list_off, list_img, sorted_img, sorted_pos, host, enable=True, status=None):
+    """Covisibility clusters of every query's database list on the device (csrc/covis_spec.h, steps 2 and 3).  Device tensors: kp_off int32
+    [n_images+1], point_of_keypoint int32 [n_nodes] (flat; -1: none), obs_offsets int32 [T+1] and obs_image int32 [N_obs] of the points,
+    list_off int32 [Q+1] and list_img int32 [L] (every query's database images in order of first appearance), sorted_img / sorted_pos int32
+    [L] (each list sorted by image id, with the positions).  host: dict(list_off, list_img) - numpy copies of the two small tables, which
+    the entry point checks before it enqueues (a list above 1024 entries, an image that does not exist: GeoFormerHipError).  Two positions
+    are linked iff a point has an observation in both images; a cluster is a connected component on the list alone.  Returns (cluster int32
+    [L]: the cluster number of every position, numbered in ascending order of a cluster's smallest position; n_clusters int32 [Q]; status
+    int32 [1]: bits set on the device for tables that name what does not exist - the caller reads it with its sizes).  enable=False: every
+    position has cluster 0.  One launch, one workgroup per query, no host synchronisation; the same bytes in every run."""
+    _need_cuda(kp_off, point_of_keypoint, obs_offsets, obs_image, list_off, list_img, sorted_img, sorted_pos)
+    dev = kp_off.device
+    Q, Lt = int(list_off.numel()) - 1, int(list_img.numel())
+    n_images, n_nodes, T, n_obs = int(kp_off.numel()) - 1, int(point_of_keypoint.numel()), int(obs_offsets.numel()) - 1, int(obs_image.numel())
+    if Q < 0 or n_images < 0 or T < 0 or sorted_img.numel() != Lt or sorted_pos.numel() != Lt:
+        raise ValueError('covis_clusters: kp_off [n_images+1], obs_offsets [T+1], list_off [Q+1], list_img / sorted_img / sorted_pos [L]')
+    loh, lop = _host_i32(host['list_off'])
+    lih, lip = _host_i32(host['list_img'])
+    if loh.size != Q + 1 or lih.size != Lt:
+        raise ValueError('covis_clusters: the host copies differ in size from the device tables')
+    cluster = torch.zeros(max(Lt, 1), dtype=torch.int32, device=dev)
+    ncl = torch.zeros(max(Q, 1), dtype=torch.int32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev) if status is None else status
+    check(_lib.lib().gf_covis_cluster(_p(_i32(kp_off, dev)), n_images, _p(_i32(point_of_keypoint, dev)), n_nodes, _p(_i32(obs_offsets, dev)), T,
+                                      _p(_i32(obs_image, dev)), n_obs, lop, lip, _p(_i32(list_off, dev)), _p(_i32(list_img, dev)),
+                                      _p(_i32(sorted_img, dev)), _p(_i32(sorted_pos, dev)), Q, Lt, int(bool(enable)), _p(cluster), _p(ncl),
+                                      _p(status), _stream()), 'gf_covis_cluster')
+    return cluster[:Lt], ncl[:Q], status
+
+
+def sparse_rows(pairs, pair_row_off, ids, kp_off, point_of_keypoint, n_points, list_off, cluster, n_clusters, host, dedup=False, status=None,
+                keypoints=None, points=None):
+    """The 2-D - 3-D rows of sparse localisation on the device, in problem order (csrc/covis_spec.h, steps 4 - 6).  Device tensors: pairs
+    int32 [C,8] (the contributing pairs in pair order: query index, query image, database image, first and end row in ids, the query's
+    column of ids, the database image's position in its query's list, 0), pair_row_off int32 [C+1] (the prefix sum of their row counts),
+    ids int32 [E,2], kp_off, point_of_keypoint (flat), list_off int32 [Q+1], and cluster / n_clusters as covis_clusters returns them.
+    n_points: T.  host: dict(pairs) - the numpy copy the entry point checks before it enqueues.  gf_sparse_rows writes per original row the
+    query keypoint's node, the point, the problem (query-major, then cluster number) and keep (the database keypoint has a point); the
+    stable order by problem and, with dedup, the first occurrence of every (query keypoint, point) inside a problem are torch's stable
+    sorts and scans.  One device-to-host read (N problems, M rows, the status words; tables that name what does not exist raise after it).
+    Returns dict(row_kp, row_pt, row_prob int32 [M0], keep uint8 [M0], first_of int32 [M0] (the original row that stands for a row: itself
+    without dedup; -1 for a row without a point), slot int32 [M0] (the RANSAC row of first_of; -1), sel int64 [M] (the original rows of
+    the RANSAC rows), prob_off int32 [N+1], prob_base int32 [Q+1], N, M, and - with keypoints fp32 [n_nodes,2] and points fp32 [T,3] -
+    p2d fp32 [M,2] and p3d fp32 [M,3])."""
+    _need_cuda(pairs, pair_row_off, ids, kp_off, point_of_keypoint, list_off, cluster, n_clusters)
+    dev = kp_off.device
+    C, E, Q = int(pairs.shape[0]), int(ids.shape[0]), int(list_off.numel()) - 1
+    n_images, n_nodes, Lt = int(kp_off.numel()) - 1, int(point_of_keypoint.numel()), int(cluster.numel())
+    if pairs.shape != (C, CV_PAIR_WORDS) or pair_row_off.numel() != C + 1 or ids.shape != (E, 2) or n_clusters.numel() != Q:
+        raise ValueError('sparse_rows: pairs [C,8], pair_row_off [C+1], ids [E,2], n_clusters [Q]')
+    ph, php = _host_i32(host['pairs'])
+    if ph.size != C * CV_PAIR_WORDS:
+        raise ValueError('sparse_rows: the host copy of pairs differs in size from the device table')
+    M0 = int((ph.reshape(-1, CV_PAIR_WORDS)[:, 4].astype('int64') - ph.reshape(-1, CV_PAIR_WORDS)[:, 3]).sum()) if C else 0
+    if M0 >= 2 ** 31:
+        raise _lib.GeoFormerHipError('sparse_rows: 2^31 rows or more')
+    prob_base = torch.zeros(Q + 1, dtype=torch.int32, device=dev)
+    prob_base[1:] = torch.cumsum(n_clusters.to(torch.int64), 0).to(torch.int32)
+    rows = max(M0, 1)
+    row_kp, row_pt, row_prob = (torch.full((rows,), -1, dtype=torch.int32, device=dev) for _ in range(3))
+    keep = torch.zeros(rows, dtype=torch.uint8, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev) if status is None else status
+    check(_lib.lib().gf_sparse_rows(php, _p(_i32(pairs, dev)), _p(_i32(pair_row_off, dev)), C, M0, _p(_i32(ids, dev)), E, _p(_i32(kp_off, dev)),
+                                    n_images, _p(_i32(point_of_keypoint, dev)), n_nodes, int(n_points), _p(_i32(list_off, dev)),
+                                    _p(_i32(cluster, dev)), Lt, _p(prob_base), Q, _p(row_kp), _p(row_pt), _p(row_prob), _p(keep), _p(status),
+                                    _stream()), 'gf_sparse_rows')
+    row_kp, row_pt, row_prob, keep = row_kp[:M0], row_pt[:M0], row_prob[:M0], keep[:M0]
+    kept = keep.bool()
+    # kept rows first, in (problem, original row) order: a stable sort by problem with the dropped rows behind every problem
+    big = torch.iinfo(torch.int32).max
+    order = torch.sort(torch.where(kept, row_prob, torch.full_like(row_prob, big)), stable=True).indices       # [M0] original rows
+    ar = torch.arange(M0, dtype=torch.int64, device=dev)
+    first_of = torch.where(kept, ar, torch.full_like(ar, -1))
+    if dedup and M0:
+        # runs of equal (problem, keypoint, point): three stable sorts, least significant key first; a run's head is its earliest row
+        perm = ar
+        for key in (row_pt, row_kp, torch.where(kept, row_prob, torch.full_like(row_prob, big))):
+            perm = perm[torch.sort(key[perm], stable=True).indices]
+        a, b, c = row_prob[perm], row_kp[perm], row_pt[perm]
+        head = torch.ones(M0, dtype=torch.bool, device=dev)
+        head[1:] = (a[1:] != a[:-1]) | (b[1:] != b[:-1]) | (c[1:] != c[:-1])
+        head_at = torch.cummax(torch.where(head, ar, torch.zeros_like(ar)), 0).values
+        first = torch.empty_like(ar)
+        first[perm] = perm[head_at]
+        first_of = torch.where(kept, first, first_of)
+    rep = kept & (first_of == ar)                                      # the rows RANSAC sees
+    rep_sorted = rep[order]
+    pos = torch.cumsum(rep_sorted.to(torch.int64), 0) - 1
+    slot_of_row = torch.full((M0,), -1, dtype=torch.int64, device=dev)
+    slot_of_row[order] = torch.where(rep_sorted, pos, torch.full_like(pos, -1))
+    slot = torch.where(kept, slot_of_row[first_of.clamp(min=0)], torch.full_like(ar, -1)) if M0 else slot_of_row
+    n_prob = prob_base[-1:].to(torch.int64)
+    sizes = torch.cat([n_prob, rep.sum().reshape(1), status.to(torch.int64)]).cpu()          # the one device-to-host read
+    N, M = int(sizes[0]), int(sizes[1])
+    _cv_raise('sparse_rows', int(sizes[2]))
+    sel = order[torch.sort((~rep_sorted).to(torch.int8), stable=True).indices[:M]]        # (M is known: no second read for a mask's size)
+    per_prob = torch.zeros(N + 1, dtype=torch.int64, device=dev)
+    if M:
+        per_prob.scatter_add_(0, row_prob[sel].to(torch.int64) + 1, torch.ones(M, dtype=torch.int64, device=dev))
+    out = {'row_kp': row_kp, 'row_pt': row_pt, 'row_prob': row_prob, 'keep': keep, 'first_of': first_of.to(torch.int32), 'slot': slot.to(torch.int32),
+           'sel': sel, 'prob_off': torch.cumsum(per_prob, 0).to(torch.int32), 'prob_base': prob_base, 'N': N, 'M': M}
+    if keypoints is not None and points is not None:
+        out['p2d'] = keypoints[row_kp[sel].long()] if M else keypoints.new_zeros(0, 2)
+        out['p3d'] = points[row_pt[sel].long()] if M else points.new_zeros(0, 3)
+    return out
+
+
+def select_cluster(prob_base, rs, row_prob, slot, min_inliers=12):
+    """The winning cluster of every query and the masks on the original rows, on the device (csrc/covis_spec.h, steps 8 and 9).  prob_base
+    int32 [Q+1], rs: what ransac_absolute_pose returned for the N = prob_base[-1] problems, row_prob / slot int32 [M0] as sparse_rows
+    returns them.  The winner of a query is its valid problem with the most inliers, then the lowest cluster number.  Returns dict(winner
+    int32 [Q] (cluster number; -1), localized int32 [Q] (a winner with at least min_inliers inliers), R fp64 [Q,3,3], t fp64 [Q,3],
+    n_inliers, rounds int32 [Q] (the winner's; zeros without one), cluster_inliers int32 [N] (the inliers of every problem; 0 where
+    RANSAC found no model), mask uint8 [M0] (a row of a winning problem: the inlier byte of its slot; 0 otherwise)).  No host
+    synchronisation."""
+    _need_cuda(prob_base, row_prob, slot, rs['valid'])
+    dev = prob_base.device
+    Q, M0 = int(prob_base.numel()) - 1, int(row_prob.numel())
+    N, M = int(rs['valid'].numel()), int(rs['inliers'].numel())
+    qrows = max(Q, 1)
+    winner, localized, nin, rounds = (torch.zeros(qrows, dtype=torch.int32, device=dev) for _ in range(4))
+    Rq = torch.zeros(qrows, 3, 3, dtype=torch.float64, device=dev)
+    tq = torch.zeros(qrows, 3, dtype=torch.float64, device=dev)
+    is_win = torch.zeros(max(N, 1), dtype=torch.uint8, device=dev)
+    mask = torch.zeros(max(M0, 1), dtype=torch.uint8, device=dev)
+    check(_lib.lib().gf_covis_select(_p(_i32(prob_base, dev)), Q, N, _p(_i32(rs['valid'], dev)), _p(_i32(rs['n_inliers'], dev)), _p(_contig(rs['R'])),
+                                     _p(_contig(rs['t'])), _p(_i32(rs['rounds'], dev)), _p(_contig(rs['inliers'])), M, _p(_i32(row_prob, dev)),
+                                     _p(_i32(slot, dev)), M0, int(min_inliers), _p(winner), _p(localized), _p(Rq), _p(tq), _p(nin), _p(rounds),
+                                     _p(is_win), _p(mask), _stream()), 'gf_covis_select')
+    return {'winner': winner[:Q], 'localized': localized[:Q], 'R': Rq[:Q], 't': tq[:Q], 'n_inliers': nin[:Q], 'rounds': rounds[:Q],
+            'cluster_inliers': torch.where(rs['valid'] == 1, rs['n_inliers'], torch.zeros_like(rs['n_inliers'])), 'mask': mask[:M0]}

@@ -40,7 +40,8 @@ typedef enum { GF_F32 = 0, GF_F16 = 1, GF_BF16 = 2 } gf_dtype;
 /* Still 4 with gf_pos_encode_ptrs / gf_fine_gather_ptrs and gf_pos_encode_ragged / gf_fine_gather_ragged (with gf_map_record): entries appended at
  * the end change no existing one; a binding that needs them fails at load on the missing symbol (geoformer_amd/_lib.py binds every name).
  * Likewise with the gf_keypoint_* entries, gf_fundamental_* (gf_fundamental_ransac_lo and its workspace query included), gf_linear_rows,
- * gf_index_rows, gf_fine_rows*, gf_abspose_* and gf_xyz_lookup (with gf_xyz_map), gf_track_link, gf_track_flatten and gf_triangulate*. */
+ * gf_index_rows, gf_fine_rows*, gf_abspose_* and gf_xyz_lookup (with gf_xyz_map), gf_track_link, gf_track_flatten and gf_triangulate*,
+ * gf_covis_cluster, gf_sparse_rows and gf_covis_select. */
 #define GF_ABI_VERSION 4
 int gf_abi_version(void);
 const char* gf_last_error(void);
@@ -842,6 +843,48 @@ int gf_triangulate(const int32_t* track_off, int T, int n_obs, const int32_t* ob
                    const double* R, const double* t, int n_images, float pixel_thr, double cos_min_angle, int min_obs, int refit,
                    uint32_t seed, double* X, int32_t* valid, int32_t* conflict, int32_t* n_inliers, int32_t* hypothesis, int32_t* rounds,
                    double* err2, uint8_t* inliers, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Sparse localisation against triangulated points: covisibility clustering of a query's database images, unique 2-D - 3-D rows, and the
+ * choice of the winning cluster (what hloc's localize_sfm does with covisibility_clustering=True around pycolmap; the reference has no
+ * code for it).  hloc / pycolmap parity is unpinned; the rule is the one stated in geoformer_amd/csrc/covis_spec.h, which also compiles
+ * for the host (csrc/host/covis_host.cpp): integer work, byte-exact against that build and from run to run.
+ * The pair-level tables are the caller's (O(pairs) bookkeeping): a contributing pair is 8 int32 words (query index, query image, database
+ * image, first row and end row in ids, the column of ids holding the query's keypoint, the database image's position in its query's list,
+ * 0); list_off [Q + 1] / list_img [L_total] are the per-query database lists in order of first appearance, sorted_img / sorted_pos the
+ * same lists sorted by image id with the positions carried along.  Arrays whose names end in _host are HOST copies, read before anything
+ * is enqueued: a list above 1024 entries, an image index outside [0, n_images), a row range outside ids and totals at or above 2^31 are
+ * GF_ERR_INVALID_ARGUMENT.  What only the device sees (keypoint indices of match rows, point ids) is checked there: the row or keypoint
+ * is skipped and a bit of status int32 [1] (zeroed by the caller) is set: 1 image range, 2 keypoint range, 4 point range, 8 list range.
+ *   gf_covis_cluster
+ *     kp_off int32 [n_images + 1], point_of_keypoint int32 [n_nodes] (-1: none), obs_offsets int32 [T + 1] and obs_image int32 [n_obs] of
+ *     the points.  One workgroup per query: positions a and b of a list are linked iff a point has an observation in both images; a
+ *     cluster is a connected component on the list alone (lock-free union-find in LDS, the larger root onto the smaller).  outputs:
+ *     cluster int32 [L_total] (the cluster number of every position: clusters numbered in ascending order of their smallest position),
+ *     n_clusters int32 [Q].  enable == 0: every position has cluster 0.
+ *   gf_sparse_rows
+ *     one thread per match row of the contributing pairs (pair_row_off int32 [C + 1]: their prefix sum, last = M0).  prob_base int32
+ *     [Q + 1]: the exclusive scan of n_clusters.  outputs per row: row_kp (the node of the query keypoint), row_pt (the point of the
+ *     database keypoint, -1), row_prob (prob_base[query] + cluster of the database image), keep uint8 (1 iff the row has a point).
+ *   gf_covis_select
+ *     valid, n_inliers, R, t, rounds [N] and inliers uint8 [M] as gf_abspose_ransac wrote them for the N problems; row_prob and slot int32
+ *     [M0] (slot: the RANSAC row that stands for an original row, -1 for a dropped one).  One thread per query: the winner is its valid
+ *     problem with the most inliers, then the lowest cluster.  outputs: winner int32 [Q] (a cluster number, -1), localized int32 [Q]
+ *     (a winner with at least min_inliers inliers), Rq fp64 [Q,9], tq fp64 [Q,3], nin_q, rounds_q int32 [Q] (the winner's; zeros without
+ *     one), is_win uint8 [N], mask uint8 [M0] (a row of a winning problem: the inlier byte of its slot; every other row 0).
+ * ------------------------------------------------------------------------------------------ */
+int gf_covis_cluster(const int32_t* kp_off, int n_images, const int32_t* point_of_keypoint, int n_nodes, const int32_t* obs_offsets, int T,
+                     const int32_t* obs_image, int n_obs, const int32_t* list_off_host, const int32_t* list_img_host, const int32_t* list_off,
+                     const int32_t* list_img, const int32_t* sorted_img, const int32_t* sorted_pos, int Q, int L_total, int enable,
+                     int32_t* cluster, int32_t* n_clusters, int32_t* status, void* stream);
+int gf_sparse_rows(const int32_t* pairs_host, const int32_t* pairs, const int32_t* pair_row_off, int C, int M0, const int32_t* ids, int E,
+                   const int32_t* kp_off, int n_images, const int32_t* point_of_keypoint, int n_nodes, int T, const int32_t* list_off,
+                   const int32_t* cluster, int L_total, const int32_t* prob_base, int Q, int32_t* row_kp, int32_t* row_pt, int32_t* row_prob,
+                   uint8_t* keep, int32_t* status, void* stream);
+int gf_covis_select(const int32_t* prob_base, int Q, int N, const int32_t* valid, const int32_t* n_inliers, const double* R, const double* t,
+                    const int32_t* rounds, const uint8_t* inliers, int M, const int32_t* row_prob, const int32_t* slot, int M0,
+                    int min_inliers, int32_t* winner, int32_t* localized, double* Rq, double* tq, int32_t* nin_q, int32_t* rounds_q,
+                    uint8_t* is_win, uint8_t* mask, void* stream);
 
 #ifdef __cplusplus
 }
