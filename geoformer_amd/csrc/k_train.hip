@@ -369,8 +369,8 @@ extern "C" int gf_activation_backward(const void* dh, const void* h, void* dz, s
 // that the accumulator's column is the lane's own token and everything per token (den, dout . num, phi') is lane-local arithmetic plus
 // one exchange between the wave halves; an accumulator is packed as it stands into the next product's operand.  The two state sums
 // contract over TOKENS: their operands are transposes of token tiles, read with ds_read_b64_tr_b16 from [token][64 B] LDS images
-// (wave-private, no workgroup barrier in the loop); Ksum / dKsum ride along as a product with a column of ones / of dden.  16-bit
-// operands (phi(q), phi(k), v / S, the states, dnum, dden rounded to the storage type), fp32 accumulation; per-(image, head) states by
+// (wave-private, no workgroup barrier in the loop); Ksum / dKsum ride along as a product with a column of ones / of -(dout . num) / den.  16-bit
+// operands (phi(q), phi(k), v / S, the states, phi(q) S / den, -(dout . num) / den rounded to the storage type), fp32 accumulation; per-(image, head) states by
 // chunk partials added in chunk order (deterministic).  Five launches: state partials, sum, per-query pass (+ gradient-state partials),
 // sum, per-source pass.
 // =====================================================================================================================
@@ -541,7 +541,7 @@ __global__ __launch_bounds__(256) void lb_state_sum(const float* part, float* st
     }
 }
 
-// per-query pass: dq, and the partials of the gradient state dKV = Q^T dnum, dKsum = Q^T dden
+// per-query pass: dq, and the partials of the gradient state dKV = Q^T dnum = (Q z)^T dout, dKsum = Q^T dden = (Q z)^T w
 template <typename T>
 __global__ __launch_bounds__(256) void lb_query_pass(LbArgs a) {
     using M = Mma32<T>;
@@ -600,27 +600,34 @@ __global__ __launch_bounds__(256) void lb_query_pass(LbArgs a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) dot += ga[r] * num[r];
         dot += __shfl_xor(dot, 32, 64);
-        const float z = sl / den, dden = live ? -dot * z / den : 0.f;
-        float dnum[16];
+        // z = S / den stays out of every 16-bit operand: it passes the storage type's range long before a gradient does (cold q: den ~ phi(q);
+        // an image without a valid key: den = eps and S / eps = inf in fp16, inf x the zero state = NaN).  dq takes z in fp32 after the
+        // product with dout as stored; the gradient state takes it on phi(q), where phi(q) z ~ S / Ksum whatever q is, against dout as stored
+        // and -(dout . num) / den (dden = that x z)
+        const float z = sl / den, w = live ? -dot / den : 0.f, dden = w * z;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) dnum[r] = live ? ga[r] * z : 0.f;
+        for (int r = 0; r < 16; ++r) ga[r] = live ? ga[r] : 0.f;
         v16f dqt;
 #pragma unroll
         for (int r = 0; r < 16; ++r) dqt[r] = 0.f;
 #pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) M::mma(kvr[s2], lb_pack<T>(dnum + 8 * s2), dqt);   // rows d, column = the lane's token
+        for (int s2 = 0; s2 < 2; ++s2) M::mma(kvr[s2], lb_pack<T>(ga + 8 * s2), dqt);     // rows d, column = the lane's token
         float dq[16];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) dq[r] = live ? (dqt[r] + dden * ksr[r]) * (qa[r] > 0.f ? 1.f : __expf(qa[r])) : 0.f;
+        for (int r = 0; r < 16; ++r) dq[r] = live ? (dqt[r] * z + dden * ksr[r]) * (qa[r] > 0.f ? 1.f : __expf(qa[r])) : 0.f;
         if (l < a.L) lb_store_acc<T>((T*)a.dq + ((size_t)n * a.L + l) * (a.H * LB_D) + hh * LB_D, h, dq);
-        // the tile's Q, dnum and dden rows -> images, then their transposes as operands of the gradient state
+        // the tile's Q z, dout and w rows -> images, then their transposes as operands of the gradient state
 #pragma unroll
-        for (int g = 0; g < 2; ++g) *reinterpret_cast<LFrag<T>*>(qimg + lr * 64 + (16 * g + 8 * h) * 2) = qf[g];
+        for (int g = 0; g < 2; ++g) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) qq[g][j] = live ? qq[g][j] * z : 0.f;
+            *reinterpret_cast<LFrag<T>*>(qimg + lr * 64 + (16 * g + 8 * h) * 2) = lb_pack<T>(qq[g]);
+        }
 #pragma unroll
         for (int j4 = 0; j4 < 4; ++j4)
             *reinterpret_cast<gf_vec<T, 4>*>(dimg + lr * 64 + (8 * j4 + 4 * h) * 2) =
-                gf_vec<T, 4>{(T)dnum[4 * j4], (T)dnum[4 * j4 + 1], (T)dnum[4 * j4 + 2], (T)dnum[4 * j4 + 3]};
-        if (h == 0) *reinterpret_cast<T*>(wimg + lr * 64) = (T)dden;
+                gf_vec<T, 4>{(T)ga[4 * j4], (T)ga[4 * j4 + 1], (T)ga[4 * j4 + 2], (T)ga[4 * j4 + 3]};
+        if (h == 0) *reinterpret_cast<T*>(wimg + lr * 64) = (T)w;
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
@@ -741,7 +748,7 @@ extern "C" int gf_linear_attention_backward(const void* q, const void* k, const 
 // at once the B operand of the per-token products and lane-local for phi' / den / dout . num; the token-contracting products (KV, dKV and
 // their transposes - both orientations are multiplied, which saves transposing an accumulator - and the row sums against a column of
 // ones) read transposes of [token][64 B] LDS images with ds_read_b64_tr_b16; every state operand of the per-token products is an
-// accumulator packed as it stands.  16-bit operands (phi(q), phi(k), vs, the states, dnum, dden phi(q)), fp32 accumulation.
+// accumulator packed as it stands.  16-bit operands (phi(q), phi(k), vs, the states, phi(q) Lw / den, dden phi(q)), fp32 accumulation.
 // =====================================================================================================================
 namespace {
 
@@ -796,7 +803,6 @@ __global__ __launch_bounds__(256) void window_la_backward(const T* q, const T* k
         }
         put(kimg, kp);
         put(vimg, vs);
-        put(qimg, qp);
         __builtin_amdgcn_wave_barrier();
         v16f kv, vk, ks;
         zero(kv); zero(vk); zero(ks);
@@ -828,22 +834,26 @@ __global__ __launch_bounds__(256) void window_la_backward(const T* q, const T* k
             z[e] = lw / den[e];
             dden[e] = -dot[e] * z[e] / den[e];
         }
-        float dnum[16], qw[16];
+        // z = Lw / den stays out of the 16-bit operands (it leaves fp16's range at cold q long before a gradient does): dq takes it in fp32
+        // after the product with dout as stored (the diagonal quadrants: a row's products all carry its own head's z), the gradient state
+        // on phi(q), where phi(q) z ~ Lw / ks whatever q is
+        float qz[16], qw[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            dnum[r] = ga[r] * z[r >> 3];
+            qz[r] = qp[r] * z[r >> 3];
             qw[r] = qp[r] * dden[r >> 3];
         }
         v16f dqt;
         zero(dqt);
-        M::mma(lb_pack_acc<T, 0>(vk), lb_pack<T>(dnum), dqt);        // rows d, column = the lane's token
-        M::mma(lb_pack_acc<T, 1>(vk), lb_pack<T>(dnum + 8), dqt);
+        M::mma(lb_pack_acc<T, 0>(vk), lb_pack<T>(ga), dqt);          // rows d, column = the lane's token
+        M::mma(lb_pack_acc<T, 1>(vk), lb_pack<T>(ga + 8), dqt);
         float o[16];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) o[r] = (dqt[r] + dden[r >> 3] * ks[r]) * (qa[r] > 0.f ? 1.f : __expf(qa[r]));
+        for (int r = 0; r < 16; ++r) o[r] = (dqt[r] * z[r >> 3] + dden[r >> 3] * ks[r]) * (qa[r] > 0.f ? 1.f : __expf(qa[r]));
         if (live) lb_store_acc<T>(dq + row + c0, h, o);
-        // the gradient state: dKV = Q^T dnum (both orientations), dks = (dden Q)^T 1
-        put(dimg, dnum);
+        // the gradient state: dKV = Q^T dnum = (Q z)^T dout (both orientations), dks = (dden Q)^T 1
+        put(qimg, qz);
+        put(dimg, ga);
         put(wimg, qw);
         __builtin_amdgcn_wave_barrier();
         v16f gkv, gvk, gks;
