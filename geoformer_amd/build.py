@@ -27,6 +27,7 @@ FUND_HOST_LIB = os.path.join(OBJ, 'libfund_host.so')
 ABSPOSE_HOST_LIB = os.path.join(OBJ, 'libabspose_host.so')
 TRI_HOST_LIB = os.path.join(OBJ, 'libtri_host.so')
 COVIS_HOST_LIB = os.path.join(OBJ, 'libcovis_host.so')
+BA_HOST_LIB = os.path.join(OBJ, 'libba_host.so')
 
 
 def _headers_digest():
@@ -131,6 +132,14 @@ def build_covis_host(verbose=True):
                            (os.path.join(CSRC, 'covis_spec.h'),), verbose)
 
 
+def build_ba_host(verbose=True):
+    """TEST INFRASTRUCTURE and CPU reference: the serial host form of the bundle adjustment (csrc/host/ba_host.cpp over csrc/ba_spec.h, the
+    text k_bundle.hip compiles for the device).  Only tests and tools/bundle_probe.py load it."""
+    return _build_host_lib(BA_HOST_LIB, 'ba_host.stamp', os.path.join(CSRC, 'host', 'ba_host.cpp'),
+                           tuple(os.path.join(CSRC, h) for h in ('ba_spec.h', 'tri_solver.h', 'abs_solver.h', 'fund_solver.h', 'solver_common.h',
+                                                                 'keypoint_spec.h', 'gf_hash.h')), verbose)
+
+
 def build(verbose=True, jobs=4):
     os.makedirs(OBJ, exist_ok=True)
     build_pose_host(verbose)
@@ -140,6 +149,7 @@ def build(verbose=True, jobs=4):
     build_abspose_host(verbose)
     build_tri_host(verbose)
     build_covis_host(verbose)
+    build_ba_host(verbose)
     srcs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.hip'))
     hdig = _headers_digest()
     with ThreadPoolExecutor(jobs) as ex:

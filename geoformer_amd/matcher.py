@@ -847,6 +847,142 @@ def _assemble_tracks(n, kp_off, T, X, err2, valid, conflict, toff, oimg, okp, in
                               int(T - conflict.sum() - nv))
 
 
+# ---------------------------------------------------------------------------------------------
+# bundle adjustment: the database poses and the triangulated points refined jointly (ops.bundle_adjust; the rule is csrc/ba_spec.h)
+# ---------------------------------------------------------------------------------------------
+class RefinedStructure(NamedTuple):
+    poses: dict              # name -> (R 3 x 3, t [3]) with x_cam = R X + t: every entry of the input, the free ones refined
+    tracks: TriangulatedTracks  # the points refined; only observations that are inliers at the final state, points with at least min_obs
+    cost: np.ndarray         # [stages * iters + stages] float64: the truncated cost before the first and after every iteration, per stage
+    accepted: np.ndarray     # [stages * iters] int32: 1 where the iteration's step was taken
+    n_free: int              # cameras that were free to move
+
+
+def _refine_inputs(cm, tt, intrinsics, poses, fixed):
+    """What refine uploads: dict(K fp32 [n,9], R / t fp64 with NaN for an image without a pose and t moved to the new origin, origin [3], X
+    fp64 [T,3] moved likewise, obs_off, obs_image int32, uv fp32 [N,2], free bool [n]).  Free: a pose, not named in fixed, and at least one
+    observation."""
+    n, kp_off, K, R, t, origin = _triangulation_inputs(cm, intrinsics, poses)[:6]
+    unknown = [f for f in fixed if f not in cm.names]
+    if unknown:
+        raise ValueError(f'refine: fixed names {unknown[0]!r}, which is not an image of the keypoints')
+    obs_image = np.ascontiguousarray(tt.obs_image, np.int32)
+    obs_kp = np.asarray(tt.obs_keypoint, np.int64)
+    if len(obs_image) and (obs_image.min() < 0 or obs_image.max() >= n):
+        raise ValueError('refine: the tracks name an image the keypoints do not have')
+    kps = np.concatenate([np.asarray(k, np.float32).reshape(-1, 2) for k in cm.keypoints]) if n else np.zeros((0, 2), np.float32)
+    counts = np.diff(kp_off)
+    if len(obs_image) and (obs_kp.min() < 0 or (obs_kp >= counts[obs_image]).any()):
+        raise ValueError('refine: the tracks name a keypoint its image does not have')
+    posed = np.isfinite(R).all(1) & np.isfinite(t).all(1)
+    fixed = set(fixed)
+    free = posed & np.array([name not in fixed for name in cm.names], bool) & (np.bincount(obs_image, minlength=n) > 0)
+    return dict(n=n, kp_off=kp_off, K=K, R=R, t=t, origin=origin, X=np.asarray(tt.points, np.float64).reshape(-1, 3) - origin,
+                obs_off=np.ascontiguousarray(tt.obs_offsets, np.int32), obs_image=obs_image, obs_kp=obs_kp.astype(np.int32),
+                uv=np.ascontiguousarray(kps[kp_off[obs_image].astype(np.int64) + obs_kp]), free=free, posed=posed)
+
+
+def _refine_device(a, thrs, iters, device):
+    """One upload, one ops.bundle_adjust per threshold (each from the state the one before left, all on the device), one read back ->
+    dict(R [n,9], t [n,3], X [T,3], inliers uint8 [N], cost, accepted) in numpy."""
+    n, T, N = a['n'], len(a['X']), len(a['obs_image'])
+    block = np.concatenate([x.reshape(-1).view(np.int32) for x in (np.ascontiguousarray(a['R']), np.ascontiguousarray(a['t']),
+                                                                   np.ascontiguousarray(a['X']), a['K'], a['uv'], a['obs_off'], a['obs_image'],
+                                                                   a['free'].astype(np.int32))])
+    with torch.cuda.device(device):
+        d = torch.from_numpy(block).to(device)
+        o = 0
+
+        def take(words, dtype, *shape):
+            nonlocal o
+            v = d[o:o + words].view(dtype).view(*shape)
+            o += words
+            return v
+        R, t, X = take(18 * n, torch.float64, n, 9), take(6 * n, torch.float64, n, 3), take(6 * T, torch.float64, T, 3)
+        K, uv = take(9 * n, torch.float32, n, 9), take(2 * N, torch.float32, N, 2)
+        ooff, oimg, free = take(T + 1, torch.int32, T + 1), take(N, torch.int32, N), take(n, torch.int32, n)
+        host = {'obs_off': a['obs_off'], 'obs_image': a['obs_image'], 'free': a['free']}
+        costs, accs = [], []
+        for thr in thrs:
+            rs = ops.bundle_adjust(ooff, oimg, uv, K, R, t, X, free, thr=thr, iters=iters, host=host)
+            R, t, X = rs['R'], rs['t'], rs['X']
+            costs.append(rs['cost'])
+            accs.append(rs['accepted'])
+        out = torch.cat([x.reshape(-1).view(torch.uint8) for x in (R, t, X, torch.cat(costs), torch.cat(accs), rs['inliers'])]).cpu().numpy()
+    nc, na = len(thrs) * (iters + 1), len(thrs) * iters
+    cut = np.cumsum([0, 72 * n, 24 * n, 24 * T, 8 * nc, 4 * na])
+    f64 = lambda k: out[cut[k]:cut[k + 1]].view(np.float64)
+    return dict(R=f64(0).reshape(n, 9), t=f64(1).reshape(n, 3), X=f64(2).reshape(T, 3), cost=f64(3).copy(),
+                accepted=out[cut[4]:cut[5]].view(np.int32).copy(), inliers=out[cut[5]:].copy())
+
+
+def _assemble_refined(cm, tt, poses, a, r, min_obs) -> RefinedStructure:
+    """The outputs of the device (or of the host build: the CPU tests) -> RefinedStructure, in world coordinates."""
+    n, T, origin = a['n'], len(a['X']), a['origin']
+    inl = np.asarray(r['inliers']).astype(bool)
+    point_of_obs = np.repeat(np.arange(T), np.diff(a['obs_off']))
+    valid = np.bincount(point_of_obs[inl], minlength=T) >= min_obs
+    keep = inl & valid[point_of_obs]
+    nv = int(valid.sum())
+    new_id = np.full(T, -1, np.int64)
+    new_id[valid] = np.arange(nv)
+    oimg, okp, pt = a['obs_image'][keep], a['obs_kp'][keep], new_id[point_of_obs[keep]]
+    R, t, X = r['R'].reshape(n, 3, 3), r['t'], r['X']
+    Y = np.einsum('nij,nj->ni', R[oimg], X[point_of_obs[keep]]) + t[oimg]
+    K = a['K'].astype(np.float64)[oimg]
+    e2 = (K[:, 0] * Y[:, 0] / Y[:, 2] + K[:, 2] - a['uv'][keep, 0]) ** 2 + (K[:, 4] * Y[:, 1] / Y[:, 2] + K[:, 5] - a['uv'][keep, 1]) ** 2
+    per_point = np.bincount(pt, minlength=nv)
+    err = np.sqrt(np.bincount(pt, weights=e2, minlength=nv) / np.maximum(per_point, 1))
+    pok = np.full(int(a['kp_off'][-1]), -1, np.int32)
+    pok[a['kp_off'][oimg] + okp] = pt
+    tracks = TriangulatedTracks(X[valid] + origin, err, np.concatenate([[0], np.cumsum(per_point)]).astype(np.int32), oimg.astype(np.int32),
+                                okp.astype(np.int32), [pok[a['kp_off'][i]:a['kp_off'][i + 1]].copy() for i in range(n)], tt.n_tracks,
+                                tt.n_conflict, tt.n_rejected + int(T - nv))
+    out = dict(poses)
+    for i, name in enumerate(cm.names):
+        if a['free'][i]:
+            out[name] = (R[i].copy(), t[i] - R[i] @ origin)             # t' = t + R origin
+    return RefinedStructure(out, tracks, np.asarray(r['cost']), np.asarray(r['accepted']), int(a['free'].sum()))
+
+
+def refine(cm: ConsolidatedMatches, tt: TriangulatedTracks, intrinsics, poses, fixed=(), iters=16, thr=4.0, min_obs=2,
+           device='cuda') -> RefinedStructure:
+    """Bundle adjustment on the device: the poses of the images of cm and the points of tt refined jointly, minimising the squared
+    reprojection error of tt's observations truncated at thr pixels (ops.bundle_adjust; the rule is csrc/ba_spec.h: Levenberg-Marquardt,
+    points eliminated by the Schur complement, dense Cholesky of the reduced camera system, `iters` iterations enqueued at once).  poses[name]
+    = (R, t) as triangulate takes them; fixed: names of images whose poses are trusted and stay as they are.  An image is free when it has
+    a pose, is not fixed and has an observation; more than 128 free images is a ValueError (ops.BA_MAX_FREE).  With fewer than two fixed
+    images nothing but the damping holds the frame, and the result may drift by a small similarity: fix the images whose poses are
+    trusted.  An observation takes part only while its error is below thr, so thr must exceed the reprojection error of the start or the
+    observations never join: thr may be a sequence, e.g. (20, 8, 4) - one run per threshold, each from the state the one before left.
+    Returns RefinedStructure: poses (a dict like the input), tracks (the layout of tt: only observations that are inliers at the final
+    state, points with fewer than min_obs of them dropped, errors recomputed, point_of_keypoint rebuilt), cost, accepted, n_free.  The world
+    origin is moved to the centre of the camera centres' bounding box before the upload and back afterwards, as in triangulate.  One upload,
+    one read back.  No intrinsics or distortion refinement, no robust loss other than the truncation, no re-triangulation inside the loop:
+    call triangulate again with the refined poses to win observations back."""
+    thrs = tuple(float(x) for x in (thr if isinstance(thr, (tuple, list, np.ndarray)) else (thr,)))
+    if not thrs or not all(x > 0 and np.isfinite(x) for x in thrs):
+        raise ValueError('refine: thr must be positive')
+    if not 1 <= int(iters) <= ops.BA_MAX_ITERS:
+        raise ValueError(f'refine: iters must be 1 .. {ops.BA_MAX_ITERS}')
+    if min_obs < 2:
+        raise ValueError('refine: min_obs must be at least 2')
+    a = _refine_inputs(cm, tt, intrinsics, poses, fixed)
+    if int(a['free'].sum()) > ops.BA_MAX_FREE:
+        raise ValueError(f"refine: {int(a['free'].sum())} free images, the limit is {ops.BA_MAX_FREE} (the reduced camera system is solved "
+                         'densely): name more images in fixed')
+    if len(a['X']) == 0 or len(a['obs_image']) == 0:
+        return RefinedStructure(dict(poses), tt, np.zeros(0), np.zeros(0, np.int32), int(a['free'].sum()))
+    return _assemble_refined(cm, tt, poses, a, _refine_device(a, thrs, int(iters), device), min_obs)
+
+
+def write_poses(path, poses):
+    """One line per image: `path qw qx qy qz tx ty tz` with x_cam = R X + t - what read_poses reads."""
+    with open(path, 'w') as f:
+        for name, (R, t) in poses.items():
+            f.write(' '.join([name] + [repr(float(v)) for v in (*rotation_to_quaternion(R), *np.asarray(t, np.float64).reshape(3))]) + '\n')
+
+
 def localize_queries_sparse(cm: ConsolidatedMatches, tt: TriangulatedTracks, queries, intrinsics, thr=12.0, min_inliers=12, iters=None, refit=0,
                             device='cuda', covis_cluster=False, dedup=False) -> LocalizedQueries:
     """Camera poses of query images against triangulated points: the sparse counterpart of localize_queries for datasets with database
@@ -1312,6 +1448,19 @@ def build_parser():
                     help='refit every pose on its inliers up to R times (1 .. 8; the bare flag: 4) and select the inliers again')
     ls.add_argument('--out', default=None, help='file with one line per localised query: path qw qx qy qz tx ty tz (x_cam = R X + t)')
     ls.add_argument('--device', default='cuda')
+    rf = sub.add_parser('refine', help='bundle adjustment: refine the poses and the points of `triangulate --out` jointly (no model)')
+    rf.add_argument('keypoints', metavar='KEYPOINTS_DIR', help='what `pairs --keypoints DIR` wrote')
+    rf.add_argument('--points', metavar='PTS.npz', required=True, help='what `triangulate --out` wrote for the same KEYPOINTS_DIR')
+    rf.add_argument('--poses', metavar='FILE', required=True, help='the poses the points were triangulated from: path qw qx qy qz tx ty tz')
+    rf.add_argument('--intrinsics', metavar='FILE', required=True, help='one line per image with a pose: path fx fy cx cy')
+    rf.add_argument('--fixed', metavar='FILE', default=None, help='one image name per line: poses that are trusted and do not move')
+    rf.add_argument('--iters', type=int, default=16, help='Levenberg-Marquardt iterations per threshold (1 .. 64)')
+    rf.add_argument('--thr', default='4.0', metavar='T[,T...]',
+                    help='truncation of the reprojection error in pixels; several values, e.g. 20,8,4: one run per value, coarse to fine')
+    rf.add_argument('--min-obs', type=int, default=2, help='a point with fewer inlier observations at the end is dropped (at least 2)')
+    rf.add_argument('--out', metavar='PTS2.npz', required=True, help='the refined points, in the format of `triangulate --out`')
+    rf.add_argument('--out-poses', metavar='FILE2', required=True, help='all poses, the free ones refined, in the format of --poses')
+    rf.add_argument('--device', default='cuda')
     for p in (h, q, loc):
         p.add_argument('--cache-gb', type=float, default=None,
                        help='byte budget of the feature store in GB: least recently used images are dropped and extracted again when '
@@ -1377,6 +1526,45 @@ def run_localize_sparse(args):
     return lq
 
 
+def _named_tables(cm, *tables):
+    """a relative name in a poses, intrinsics or names file is looked up both as written and relative to its file"""
+    for table, path in tables:
+        base = os.path.dirname(os.path.abspath(path))
+        for name in cm.names:
+            full = name if os.path.isabs(name) else os.path.normpath(os.path.join(base, name))
+            if name not in table and full in table:
+                table[name] = table[full]
+
+
+def run_refine(args):
+    """The `refine` sub-command: between `triangulate` and `localize-sparse` (or a second `triangulate`), from and to their files.  The
+    poses file it writes names the images as names.txt does."""
+    cm = read_consolidated(args.keypoints)
+    tt = read_triangulated(args.points)
+    if len(tt.point_of_keypoint) != len(cm.names) or any(len(p) != len(k) for p, k in zip(tt.point_of_keypoint, cm.keypoints)):
+        raise SystemExit(f'refine: {args.points} was not written for the keypoints under {args.keypoints}')
+    poses, intr = read_poses(args.poses), read_intrinsics(args.intrinsics)
+    _named_tables(cm, (poses, args.poses), (intr, args.intrinsics))
+    fixed = []
+    if args.fixed:
+        fbase = os.path.dirname(os.path.abspath(args.fixed))
+        known = {(nm if os.path.isabs(nm) else os.path.normpath(os.path.join(fbase, nm))): nm for nm in cm.names}
+        with open(args.fixed) as f:
+            for line in f:
+                q = line.strip()
+                if q and not q.startswith('#'):
+                    fixed.append(q if q in cm.names else known.get(q if os.path.isabs(q) else os.path.normpath(os.path.join(fbase, q)), q))
+    rs = refine(cm, tt, intr, {nm: poses[nm] for nm in cm.names if nm in poses}, fixed, args.iters, args.thr, args.min_obs, device=args.device)
+    write_triangulated(args.out, rs.tracks)
+    write_poses(args.out_poses, rs.poses)
+    print(f'{rs.n_free} free and {len(rs.poses) - rs.n_free} fixed images, {len(tt.points)} points, {len(tt.obs_image)} observations: cost '
+          f'{float(rs.cost[0]) if len(rs.cost) else 0.0:.6g} -> {float(rs.cost[-1]) if len(rs.cost) else 0.0:.6g} in {int(rs.accepted.sum())} '
+          f'accepted of {len(rs.accepted)} iterations (thr {",".join(repr(x) for x in args.thr)} px); {len(rs.tracks.points)} points and '
+          f'{len(rs.tracks.obs_image)} observations kept, median reprojection error '
+          f'{float(np.median(rs.tracks.errors)) if len(rs.tracks.errors) else 0.0:.3f} px -> {args.out}, {args.out_poses}')
+    return rs
+
+
 def run_triangulate(args):
     """The `triangulate` sub-command: names.txt lists the images as the pair list named them, so a relative name in the poses and
     intrinsics files is looked up both as written and relative to its file."""
@@ -1399,13 +1587,22 @@ def run_triangulate(args):
 
 
 def main(argv=None):
-    """`python -m geoformer_amd.matcher match|hpatches|pairs|localize|triangulate|localize-sparse ...` (arguments: build_parser)."""
+    """`python -m geoformer_amd.matcher match|hpatches|pairs|localize|triangulate|refine|localize-sparse ...` (arguments: build_parser)."""
     ap = build_parser()
     args = ap.parse_args(argv)
     if args.cmd == 'triangulate':                                       # no model: keypoints, matches and poses in, points out
         if args.min_obs < 2 or not 0 <= args.refit <= 8 or not args.thr > 0:
             ap.error('triangulate: need --min-obs >= 2, --refit 0 .. 8 and --thr > 0')
         run_triangulate(args)
+        return
+    if args.cmd == 'refine':                                            # no model: keypoints, points and poses in, points and poses out
+        try:
+            args.thr = tuple(float(x) for x in str(args.thr).split(','))
+        except ValueError:
+            ap.error('refine: --thr takes numbers separated by commas')
+        if not 1 <= args.iters <= 64 or args.min_obs < 2 or not all(x > 0 for x in args.thr):
+            ap.error('refine: need --iters 1 .. 64, --min-obs >= 2 and --thr > 0')
+        run_refine(args)
         return
     if args.cmd == 'localize-sparse':                                   # no model either: keypoints, matches and points in, poses out
         if not 0 <= args.refit <= 8 or not args.thr > 0:

@@ -1428,6 +1428,82 @@ def triangulate_tracks(track_off, obs_image, obs_uv, K, R, t, pixel_thr=4.0, min
 
 
 # ---------------------------------------------------------------------------------------------
+# bundle adjustment: poses and points refined jointly (csrc/k_bundle.hip over csrc/ba_spec.h)
+# ---------------------------------------------------------------------------------------------
+BA_MAX_FREE = 128               # ba_spec.h: the reduced camera system is dense, at most 768 x 768
+BA_MAX_ITERS = 64
+BA_FLAG_STEP_FAILED, BA_FLAG_POINT_HELD, BA_FLAG_FREE_NO_POSE = 1, 2, 4     # bits of the status word
+
+
+def bundle_adjust(obs_off, obs_image, obs_uv, K, R, t, X, free, thr=4.0, iters=16, host=None):
+    """Camera poses and 3-D points refined jointly on the device (csrc/ba_spec.h): Levenberg-Marquardt on the truncated squared
+    reprojection error, the points eliminated by the Schur complement, the reduced camera system solved by a dense Cholesky.  Device
+    tensors: obs_off int32 [T+1], obs_image int32 [N_obs], obs_uv fp32 [N_obs,2] (the observations of every point, as TriangulatedTracks
+    holds them), K [n_images,3,3] fp32, R [n_images,3,3] and t [n_images,3] fp64 (x_cam = R X + t; NaN: an image without a pose, it takes
+    no part and keeps its bits), X fp64 [T,3], free bool [n_images] (the cameras that move; every other one is fixed).  host: dict(obs_off,
+    obs_image, free) - numpy copies of the three small tables, which the entry point checks before it enqueues; without it they are read
+    back from the device here.  More than 128 free cameras is a ValueError.  The image-major index of the observations is torch's stable
+    sort.  Returns dict(R, t, X, inliers uint8 [N_obs] (takes part at the final state), n_inliers int32 [T], cost fp64 [iters+1] (never
+    increases), accepted int32 [iters], lam fp64 [iters+1], status int32 [1] (BA_FLAG_* bits)).  All iterations are enqueued at once, the
+    decision to accept a step is taken on the device; no host synchronisation; bit-identical from run to run and to the host build."""
+    import numpy as np
+    _need_cuda(obs_off, obs_image, obs_uv)
+    dev = obs_off.device
+    T, n_obs = int(obs_off.numel()) - 1, int(obs_image.numel())
+    if T < 1 or n_obs < 1 or obs_uv.shape != (n_obs, 2):
+        raise ValueError('bundle_adjust: obs_off [T+1], obs_image [N_obs], obs_uv [N_obs,2] with at least one point and one observation')
+    Kt = _contig(torch.as_tensor(K, dtype=torch.float32, device=dev).reshape(-1, 9))
+    Rt = _contig(torch.as_tensor(R, dtype=torch.float64, device=dev).reshape(-1, 9))
+    tt = _contig(torch.as_tensor(t, dtype=torch.float64, device=dev).reshape(-1, 3))
+    Xt = _contig(torch.as_tensor(X, dtype=torch.float64, device=dev).reshape(-1, 3))
+    n_images = int(Kt.shape[0])
+    if Rt.shape[0] != n_images or tt.shape[0] != n_images or Xt.shape[0] != T or n_images < 1:
+        raise ValueError(f'bundle_adjust: {n_images} K but {Rt.shape[0]} R and {tt.shape[0]} t; {T} points but {Xt.shape[0]} X')
+    if not 1 <= int(iters) <= BA_MAX_ITERS:
+        raise ValueError(f'bundle_adjust: iters must be 1 .. {BA_MAX_ITERS}')
+    if not (float(thr) > 0 and math.isfinite(float(thr))):
+        raise ValueError('bundle_adjust: thr must be positive and finite')
+    free_d = torch.as_tensor(free, device=dev).reshape(-1) != 0
+    if host is None:
+        host = {'obs_off': obs_off.cpu().numpy(), 'obs_image': obs_image.cpu().numpy(), 'free': free_d.cpu().numpy()}
+    free_h = np.asarray(host['free']).reshape(-1) != 0
+    if free_h.size != n_images:
+        raise ValueError(f'bundle_adjust: {n_images} images but {free_h.size} free flags')
+    F = int(free_h.sum())
+    if F > BA_MAX_FREE:
+        raise ValueError(f'bundle_adjust: {F} free cameras, the limit is {BA_MAX_FREE} (the reduced camera system is solved densely): fix more images')
+    ooh, oop = _host_i32(host['obs_off'])
+    oih, oip = _host_i32(host['obs_image'])
+    if ooh.size != T + 1 or oih.size != n_obs:
+        raise ValueError('bundle_adjust: the host copies differ in size from the device tables')
+    if n_obs and (oih.min() < 0 or oih.max() >= n_images):
+        raise ValueError('bundle_adjust: an observation names an image outside [0, n_images)')
+    # the image-major index: a stable sort of the observations by image, here on the host copy and there on the device - the same order
+    ioh, iop = _host_i32(np.argsort(oih, kind='stable'))
+    ifh, ifp = _host_i32(np.concatenate([[0], np.cumsum(np.bincount(oih, minlength=n_images))]))
+    cfh, cfp = _host_i32(np.where(free_h, np.cumsum(free_h) - 1, -1))
+    toff, oimg, ouv = _i32(obs_off, dev), _i32(obs_image, dev), _contig(obs_uv.to(torch.float32))
+    img_obs = torch.sort(oimg, stable=True).indices.to(torch.int32)
+    img_off = torch.cat([toff.new_zeros(1), torch.cumsum(torch.bincount(oimg.long(), minlength=n_images), 0).to(torch.int32)])
+    cam_free = torch.where(free_d, torch.cumsum(free_d.to(torch.int32), 0, dtype=torch.int32) - 1, torch.full_like(img_off[:n_images], -1))
+    cam_free = _contig(cam_free.to(torch.int32))
+    Ro, to, Xo = torch.empty_like(Rt), torch.empty_like(tt), torch.empty_like(Xt)
+    inl = torch.zeros(n_obs, dtype=torch.uint8, device=dev)
+    nin = torch.zeros(T, dtype=torch.int32, device=dev)
+    cost = torch.zeros(int(iters) + 1, dtype=torch.float64, device=dev)
+    lam = torch.zeros(int(iters) + 1, dtype=torch.float64, device=dev)
+    acc = torch.zeros(int(iters), dtype=torch.int32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    L_ = _lib.lib()
+    ws = _ws.get('bundle_adjust', L_.gf_bundle_workspace_bytes(T, n_obs, n_images, F), dev)
+    check(L_.gf_bundle_adjust(oop, oip, ifp, iop, cfp, _p(toff), T, n_obs, _p(oimg), _p(ouv), _p(img_off), _p(img_obs), _p(cam_free), n_images, F,
+                              _p(Kt), _p(Rt), _p(tt), _p(Xt), float(thr), int(iters), _p(Ro), _p(to), _p(Xo), _p(inl), _p(nin), _p(cost), _p(acc),
+                              _p(lam), _p(status), _p(ws), ws.numel(), _stream()), 'gf_bundle_adjust')
+    return {'R': Ro.view(n_images, 3, 3), 't': to, 'X': Xo, 'inliers': inl, 'n_inliers': nin, 'cost': cost, 'accepted': acc, 'lam': lam,
+            'status': status}
+
+
+# ---------------------------------------------------------------------------------------------
 # sparse localisation: covisibility clusters, unique 2-D - 3-D rows, the winning cluster (csrc/k_covis.hip over csrc/covis_spec.h)
 # ---------------------------------------------------------------------------------------------
 CV_MAX_LIST = 1024              # covis_spec.h: the longest database list of one query

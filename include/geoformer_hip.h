@@ -41,7 +41,7 @@ typedef enum { GF_F32 = 0, GF_F16 = 1, GF_BF16 = 2 } gf_dtype;
  * the end change no existing one; a binding that needs them fails at load on the missing symbol (geoformer_amd/_lib.py binds every name).
  * Likewise with the gf_keypoint_* entries, gf_fundamental_* (gf_fundamental_ransac_lo and its workspace query included), gf_linear_rows,
  * gf_index_rows, gf_fine_rows*, gf_abspose_* and gf_xyz_lookup (with gf_xyz_map), gf_track_link, gf_track_flatten and gf_triangulate*,
- * gf_covis_cluster, gf_sparse_rows and gf_covis_select. */
+ * gf_covis_cluster, gf_sparse_rows and gf_covis_select, gf_bundle_workspace_bytes and gf_bundle_adjust. */
 #define GF_ABI_VERSION 4
 int gf_abi_version(void);
 const char* gf_last_error(void);
@@ -885,6 +885,36 @@ int gf_covis_select(const int32_t* prob_base, int Q, int N, const int32_t* valid
                     const int32_t* rounds, const uint8_t* inliers, int M, const int32_t* row_prob, const int32_t* slot, int M0,
                     int min_inliers, int32_t* winner, int32_t* localized, double* Rq, double* tq, int32_t* nin_q, int32_t* rounds_q,
                     uint8_t* is_win, uint8_t* mask, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Bundle adjustment: camera poses and 3-D points refined jointly (what hloc leaves to COLMAP's bundle adjuster; the reference has no code
+ * for it).  COLMAP / Ceres parity is unpinned; the rule is the one stated in geoformer_amd/csrc/ba_spec.h - Levenberg-Marquardt on the
+ * truncated squared reprojection error, the points eliminated (Schur complement), the 6F x 6F reduced camera system solved by a dense
+ * Cholesky, every sum in a stated order - which also compiles for the host (csrc/host/ba_host.cpp): bit-exact against that build and from
+ * run to run.
+ *   gf_bundle_adjust
+ *     Arrays whose names end in _host are HOST copies of the device tables of the same name, read before anything is enqueued.
+ *     obs_off int32 [T + 1] (first 0, last n_obs, ascending: the observations of point p), obs_image int32 [n_obs], obs_uv fp32 [n_obs,2]
+ *     pixels; img_off int32 [n_images + 1] / img_obs int32 [n_obs]: the same observations by image, ascending inside an image; cam_free
+ *     int32 [n_images]: the free cameras numbered 0 .. F - 1 in ascending order of the image, -1 for a fixed one.  K fp32 [n_images,9],
+ *     R_in fp64 [n_images,9], t_in fp64 [n_images,3] with x_cam = R X + t (NaN: an image without a pose - its observations take no part, and
+ *     it keeps its bits), X_in fp64 [T,3].  thr > 0 (pixels: an observation takes part while its point is in front and its error below
+ *     thr; every other one counts thr^2), 1 <= iters <= 64, F <= 128, T, n_obs, n_images >= 1, consistent tables: anything else is
+ *     GF_ERR_INVALID_ARGUMENT.  F = 0 refines the points alone.
+ *     outputs: R_out, t_out, X_out (images that are fixed or without a pose: the input bits), inliers uint8 [n_obs] (takes part at the final
+ *     state), n_inliers int32 [T], cost fp64 [iters + 1] (never increases), accepted int32 [iters], lambda fp64 [iters + 1], status int32 [1]:
+ *     1 a step failed and was rejected (the factorisation met a pivot that was not positive, or an update was not finite), 2 a point was
+ *     held for an iteration (its damped 3 x 3 system failed the pivot test), 4 a free image has no pose.
+ *     workspace: gf_bundle_workspace_bytes(T, n_obs, n_images, F) bytes.  All iterations are enqueued at once: the decision to accept a
+ *     step is taken on the device.  No host synchronisation.
+ * ------------------------------------------------------------------------------------------ */
+size_t gf_bundle_workspace_bytes(int T, int n_obs, int n_images, int F);
+int gf_bundle_adjust(const int32_t* obs_off_host, const int32_t* obs_image_host, const int32_t* img_off_host, const int32_t* img_obs_host,
+                     const int32_t* cam_free_host, const int32_t* obs_off, int T, int n_obs, const int32_t* obs_image, const float* obs_uv,
+                     const int32_t* img_off, const int32_t* img_obs, const int32_t* cam_free, int n_images, int F, const float* K,
+                     const double* R_in, const double* t_in, const double* X_in, float thr, int iters, double* R_out, double* t_out,
+                     double* X_out, uint8_t* inliers, int32_t* n_inliers, double* cost, int32_t* accepted, double* lambda, int32_t* status,
+                     void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
