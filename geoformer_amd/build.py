@@ -136,7 +136,7 @@ def build_ba_host(verbose=True):
     """TEST INFRASTRUCTURE and CPU reference: the serial host form of the bundle adjustment (csrc/host/ba_host.cpp over csrc/ba_spec.h, the
     text k_bundle.hip compiles for the device).  Only tests and tools/bundle_probe.py load it."""
     return _build_host_lib(BA_HOST_LIB, 'ba_host.stamp', os.path.join(CSRC, 'host', 'ba_host.cpp'),
-                           tuple(os.path.join(CSRC, h) for h in ('ba_spec.h', 'tri_solver.h', 'abs_solver.h', 'fund_solver.h', 'solver_common.h',
+                           tuple(os.path.join(CSRC, h) for h in ('ba_spec.h', 'ba_pcg_spec.h', 'tri_solver.h', 'abs_solver.h', 'fund_solver.h', 'solver_common.h',
                                                                  'keypoint_spec.h', 'gf_hash.h')), verbose)
 
 

@@ -43,8 +43,14 @@
 //  11  limits       1 <= iters <= BA_MAX_ITERS (64), thr > 0 and finite, F <= BA_MAX_FREE (128), T and n_obs below 2^31, consistent tables:
 //                   anything else is an error of the entry point, never a wrapped index.  F = 0 is legal: every point on its own.
 //
-// NOT part of this: intrinsics or distortion, more than 128 free cameras (needs a sparse or iterative reduced solve), robust losses other
-// than the truncation, re-triangulation inside the loop.
+// Rules 6 and 7 have a second form, 6' and 7' - 7''' in ba_pcg_spec.h: the same reduced system solved by matrix-free preconditioned
+// conjugate gradients (per-camera blocks U + lambda diag(U) - sum Tm W^T as the preconditioner, q = S p in two sweeps over the
+// observations, every sum of many terms by 256 partials and ba_block_tree), for up to BA_PCG_MAX_FREE (65536) free cameras.  Rules 1 - 5
+// and 8 - 11 are shared as they stand; the dense form keeps its limit of BA_MAX_FREE.
+//
+// NOT part of this: intrinsics or distortion, more than 128 free cameras with the dense solve (ba_pcg_spec.h takes 65536), a
+// preconditioner other than block Jacobi or an adaptive tolerance for the iterative one, robust losses other than the truncation,
+// re-triangulation inside the loop.
 #pragma once
 #include "tri_solver.h"
 

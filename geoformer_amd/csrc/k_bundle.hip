@@ -20,8 +20,19 @@
 //   ba_final       : one thread per image and per point: the outputs from the current state.
 // One stream, no host synchronisation: all iterations are enqueued up front, and a rejected one costs its build and solve.  Integer atomics
 // only (status bits), so every output is the same in every run.
+//
+// The second solver (gf_bundle_adjust_pcg; the rule is ba_pcg_spec.h) replaces ba_camera_rows and ba_cholesky by matrix-free preconditioned
+// conjugate gradients; S is never stored.  Every reduction across cameras is a launch boundary: no workgroup waits for another one.
+//   ba_pcg_setup   : one workgroup per free camera, thread t owns partial t of the 54 sums of rule 6' (registers); the trees run through LDS
+//                    18 sums at a time; thread 0 forms Ul, M and rhs, threads 0 .. 5 one column of M^-1 each (gs_solve<6>, an LDS tile
+//                    interleaved across them); then r, z, p, x = 0 and the camera's share of <r, z>.
+//   ba_pcg_points  : one thread per point: z_p = sum W^T p.
+//   ba_pcg_cameras : one workgroup per free camera: q_f = Ul p_f - the R256 sum of Tm z_p, and the camera's share of <p, q>.
+//   ba_pcg_step    : ONE workgroup: the block trees of kappa and rho', one thread the scalar decisions, the vector updates in a strided loop,
+//                    the flag `done` and the two logs.  Once a solve has stopped or failed, the remaining CG launches read `done` and return.
 #include "gf_common.h"
 #include "ba_spec.h"
+#include "ba_pcg_spec.h"
 
 #pragma clang fp contract(off)
 
@@ -265,6 +276,223 @@ size_t ba_carve(BaArgs& a, void* base, int T, int n_obs, int n_images, int F) {
     return cv.used();
 }
 
+// ---------------------------------------------------------------------------------------------- the PCG solver (ba_pcg_spec.h)
+struct BaPcgArgs {
+    BaArgs a;                    // the shared shell; a.dc is x, a.S / a.LT / a.rhs are not there
+    BaPcgScalars* sc;
+    double* Ul;                  // [F][36]
+    double* Minv;                // [F][36]
+    double* r;                   // [6F]
+    double* z;                   // [6F]
+    double* p;                   // [6F]
+    double* q;                   // [6F]
+    double* zp;                  // [T][3]
+    double* share;               // [F] every camera's share of the inner product in flight
+    int32_t* cg_used;            // [iters]
+    double* cg_res;              // [iters]
+    double tol2;
+};
+
+#define BA_PCG_TREE 18           /* sums that go through the LDS tree together: 54 = 3 * 18 */
+
+// the pairwise tree of ba_block_tree over n arrays of 256 partials, array j at s + 256 j; the sums end in s[256 j]
+__device__ __forceinline__ void ba_pcg_trees(double* s, int n, int tid) {
+    __syncthreads();
+    for (int h = BA_BLOCK / 2; h >= 1; h >>= 1) {
+        if (tid < h)
+            for (int j = 0; j < n; ++j) s[BA_BLOCK * j + tid] = s[BA_BLOCK * j + tid] + s[BA_BLOCK * j + tid + h];
+        __syncthreads();
+    }
+}
+
+// rule 7'' over share [F]; every thread of the (one) workgroup gets the sum.  Thread t only ever reads the shares of cameras t mod 256.
+__device__ __forceinline__ double ba_pcg_reduce(const double* share, int F, double* s_red, int tid) {
+    double sum = 0.0;
+    for (int b = 0; b * BA_BLOCK < F; ++b) {
+        const int f = b * BA_BLOCK + tid;
+        s_red[tid] = f < F ? share[f] : 0.0;
+        ba_pcg_trees(s_red, 1, tid);
+        sum = sum + s_red[0];
+        __syncthreads();
+    }
+    return sum;
+}
+
+__device__ __forceinline__ int ba_pcg_image(const BaArgs& a, int f) {
+    const int img = a.free_img[f];                                     // (clamped as in ba_camera_rows)
+    return img < 0 ? 0 : (img >= a.v.n_images ? a.v.n_images - 1 : img);
+}
+
+__global__ __launch_bounds__(256) void ba_pcg_setup(BaPcgArgs g) {
+    __shared__ double s_red[BA_PCG_TREE * BA_BLOCK];
+    __shared__ double s_tot[BA_PCG_SUMS];
+    __shared__ double s_Ul[36], s_M[36], s_Minv[36], s_rhs[6], s_z[6];
+    __shared__ double s_ws[BA_PCG_WS_DOUBLES * 8];
+    __shared__ int s_part, s_ok;
+    const BaArgs& a = g.a;
+    const int tid = threadIdx.x, f = blockIdx.x;
+    int qb, qlen;
+    gs_offsets_range(a.v.img_off, ba_pcg_image(a, f), a.v.n_obs, qb, qlen);
+    const BaState s = ba_state(a, a.ctrl->cur);
+    if (tid == 0) {
+        s_part = 0;
+        s_ok = 1;
+    }
+    __syncthreads();
+    double acc[BA_PCG_SUMS];
+    GS_UNROLL
+    for (int j = 0; j < BA_PCG_SUMS; ++j) acc[j] = 0.0;
+    int any = 0;
+    for (int q = qb + tid; q < qb + qlen; q += BA_BLOCK) any |= ba_pcg_obs_terms(a.v, s, a.it, a.v.img_obs[q], acc);
+    if (any) atomicOr(&s_part, 1);
+    GS_UNROLL
+    for (int round = 0; round < BA_PCG_SUMS / BA_PCG_TREE; ++round) {
+        GS_UNROLL
+        for (int j = 0; j < BA_PCG_TREE; ++j) s_red[BA_BLOCK * j + tid] = acc[BA_PCG_TREE * round + j];
+        ba_pcg_trees(s_red, BA_PCG_TREE, tid);
+        if (tid < BA_PCG_TREE) s_tot[BA_PCG_TREE * round + tid] = s_red[BA_BLOCK * tid];
+        __syncthreads();
+    }
+    if (tid == 0) ba_pcg_blocks(s_tot, s_part, a.ctrl->lambda, s_Ul, s_M, s_rhs);
+    __syncthreads();
+    if (tid < 6 && !ba_pcg_inverse_column(s_M, tid, GsWs{s_ws + tid, 8}, s_Minv)) atomicAnd(&s_ok, 0);
+    __syncthreads();
+    if (tid < 36) {
+        g.Ul[36 * (size_t)f + tid] = s_Ul[tid];
+        g.Minv[36 * (size_t)f + tid] = s_Minv[tid];
+    }
+    if (tid == 0) {
+        if (!s_ok) {
+            a.ctrl->chol_ok = 0;
+            atomicOr(&a.ctrl->status, BA_FLAG_STEP_FAILED);
+        }
+        ba_pcg_apply6(s_Minv, s_rhs, s_z);
+        for (int k = 0; k < 6; ++k) {
+            a.dc[6 * (size_t)f + k] = 0.0;
+            g.r[6 * (size_t)f + k] = s_rhs[k];
+            g.z[6 * (size_t)f + k] = s_z[k];
+            g.p[6 * (size_t)f + k] = s_z[k];
+        }
+        g.share[f] = ba_pcg_dot6(s_rhs, s_z);
+    }
+}
+
+__global__ __launch_bounds__(256) void ba_pcg_points(BaPcgArgs g) {
+    if (g.sc->done) return;
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p < g.a.v.T) ba_pcg_point_z(g.a.v, g.a.it, p, g.p, g.zp);
+}
+
+__global__ __launch_bounds__(256) void ba_pcg_cameras(BaPcgArgs g) {
+    __shared__ double s_red[6 * BA_BLOCK];
+    __shared__ double s_u[6], s_q[6];
+    if (g.sc->done) return;
+    const BaArgs& a = g.a;
+    const int tid = threadIdx.x, f = blockIdx.x;
+    int qb, qlen;
+    gs_offsets_range(a.v.img_off, ba_pcg_image(a, f), a.v.n_obs, qb, qlen);
+    double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int q = qb + tid; q < qb + qlen; q += BA_BLOCK) ba_pcg_obs_tz(a.v, a.it, a.v.img_obs[q], g.zp, acc);
+    GS_UNROLL
+    for (int j = 0; j < 6; ++j) s_red[BA_BLOCK * j + tid] = acc[j];
+    ba_pcg_trees(s_red, 6, tid);
+    if (tid == 0) {
+        ba_pcg_apply6(g.Ul + 36 * (size_t)f, g.p + 6 * (size_t)f, s_u);
+        for (int k = 0; k < 6; ++k) {
+            s_q[k] = s_u[k] - s_red[BA_BLOCK * k];
+            g.q[6 * (size_t)f + k] = s_q[k];
+        }
+        g.share[f] = ba_pcg_dot6(g.p + 6 * (size_t)f, s_q);
+    }
+}
+
+// i < 0: the start of the solve of LM iteration iter (rho0 from the shares ba_pcg_setup left); else CG iteration i
+__global__ __launch_bounds__(256) void ba_pcg_step(BaPcgArgs g, int iter, int i) {
+    __shared__ double s_red[BA_BLOCK];
+    __shared__ BaPcgScalars s_c;
+    const int tid = threadIdx.x, F = g.a.v.F;
+    if (i >= 0 && g.sc->done) return;
+    const double sum = ba_pcg_reduce(g.share, F, s_red, tid);          // rho0, or kappa
+    if (tid == 0) {
+        BaPcgScalars c = *g.sc;
+        if (i < 0) ba_pcg_begin(c, g.a.ctrl->chol_ok, sum);
+        else ba_pcg_alpha(c, sum);
+        s_c = c;
+    }
+    __syncthreads();
+    if (i < 0 || s_c.done) {
+        if (tid == 0) {
+            if (s_c.failed) {
+                g.a.ctrl->chol_ok = 0;
+                atomicOr(&g.a.ctrl->status, BA_FLAG_STEP_FAILED);
+            }
+            *g.sc = s_c;
+            g.cg_used[iter] = s_c.used;
+            g.cg_res[iter] = s_c.res;
+        }
+        return;
+    }
+    const double alpha = s_c.alpha;
+    for (int f = tid; f < F; f += BA_BLOCK) {
+        const size_t o = 6 * (size_t)f;
+        for (int k = 0; k < 6; ++k) {
+            g.a.dc[o + k] = g.a.dc[o + k] + alpha * g.p[o + k];
+            g.r[o + k] = g.r[o + k] - alpha * g.q[o + k];
+        }
+        ba_pcg_apply6(g.Minv + 36 * (size_t)f, g.r + o, g.z + o);
+        g.share[f] = ba_pcg_dot6(g.r + o, g.z + o);
+    }
+    __syncthreads();
+    const double rho_new = ba_pcg_reduce(g.share, F, s_red, tid);
+    if (tid == 0) {
+        BaPcgScalars c = s_c;
+        ba_pcg_beta(c, rho_new, i, g.tol2);
+        s_c = c;
+        *g.sc = c;
+        g.cg_used[iter] = c.used;
+        g.cg_res[iter] = c.res;
+    }
+    __syncthreads();
+    if (s_c.done) return;
+    const double beta = s_c.beta;
+    for (int f = tid; f < F; f += BA_BLOCK)
+        for (int k = 0; k < 6; ++k) g.p[6 * (size_t)f + k] = g.z[6 * (size_t)f + k] + beta * g.p[6 * (size_t)f + k];
+}
+
+// the PCG workspace, carved (base = null: only its size): O(n_obs + T + F)
+size_t ba_pcg_carve(BaPcgArgs& g, void* base, int T, int n_obs, int n_images, int F) {
+    GfCarver cv(base);
+    BaArgs& a = g.a;
+    const size_t nf = F ? (size_t)F : 1;
+    a.ctrl = cv.take<BaCtrl>(1);
+    g.sc = cv.take<BaPcgScalars>(1);
+    a.cam_ok = cv.take<int32_t>((size_t)n_images);
+    a.obs_point = cv.take<int32_t>((size_t)n_obs);
+    a.free_img = cv.take<int32_t>(nf);
+    a.R2 = cv.take<double>(2 * 9 * (size_t)n_images);
+    a.t2 = cv.take<double>(2 * 3 * (size_t)n_images);
+    a.X2 = cv.take<double>(2 * 3 * (size_t)T);
+    a.S = nullptr; a.LT = nullptr; a.rhs = nullptr;
+    a.dc = cv.take<double>(6 * nf);
+    a.nb = (T + BA_BLOCK - 1) / BA_BLOCK;
+    a.blk = cv.take<double>((size_t)a.nb);
+    a.it.part = cv.take<uint8_t>((size_t)n_obs);
+    a.it.W = cv.take<double>(18 * (size_t)n_obs);
+    a.it.Tm = cv.take<double>(18 * (size_t)n_obs);
+    a.it.g = cv.take<double>(3 * (size_t)T);
+    a.it.Ainv = cv.take<double>(9 * (size_t)T);
+    a.it.hold = cv.take<int32_t>((size_t)T);
+    g.Ul = cv.take<double>(36 * nf);
+    g.Minv = cv.take<double>(36 * nf);
+    g.r = cv.take<double>(6 * nf);
+    g.z = cv.take<double>(6 * nf);
+    g.p = cv.take<double>(6 * nf);
+    g.q = cv.take<double>(6 * nf);
+    g.zp = cv.take<double>(3 * (size_t)T);
+    g.share = cv.take<double>(nf);
+    return cv.used();
+}
+
 }   // namespace
 
 extern "C" size_t gf_bundle_workspace_bytes(int T, int n_obs, int n_images, int F) {
@@ -324,6 +552,91 @@ extern "C" int gf_bundle_adjust(const int32_t* obs_off_host, const int32_t* obs_
             tok = gf_prof_begin("ba_cholesky", st, (double)F);
             ba_cholesky<<<1, 768, 0, st>>>(a);
             gf_prof_end("ba_cholesky", tok, st);
+        }
+        tok = gf_prof_begin("ba_update_cost", st, (double)n_obs);
+        ba_update<<<g_all, 256, 0, st>>>(a);
+        ba_cost<<<g_pts, 256, 0, st>>>(a, 1);
+        ba_decide<<<1, 1, 0, st>>>(a, iter);
+        gf_prof_end("ba_update_cost", tok, st);
+    }
+    ba_final<<<g_all, 256, 0, st>>>(a);
+    GF_CHECK_LAUNCH();
+    return GF_OK;
+}
+
+extern "C" size_t gf_bundle_pcg_workspace_bytes(int T, int n_obs, int n_images, int F) {
+    if (T <= 0 || n_obs <= 0 || n_images <= 0 || F < 0 || F > BA_PCG_MAX_FREE) return 0;
+    BaPcgArgs g;
+    return ba_pcg_carve(g, nullptr, T, n_obs, n_images, F);
+}
+
+extern "C" int gf_bundle_adjust_pcg(const int32_t* obs_off_host, const int32_t* obs_image_host, const int32_t* img_off_host,
+                                    const int32_t* img_obs_host, const int32_t* cam_free_host, const int32_t* obs_off, int T, int n_obs,
+                                    const int32_t* obs_image, const float* obs_uv, const int32_t* img_off, const int32_t* img_obs,
+                                    const int32_t* cam_free, int n_images, int F, const float* K, const double* R_in, const double* t_in,
+                                    const double* X_in, float thr, int iters, int cg_iters, double cg_tol, double* R_out, double* t_out,
+                                    double* X_out, uint8_t* inliers, int32_t* n_inliers, double* cost, int32_t* accepted, double* lambda,
+                                    int32_t* status, int32_t* cg_used, double* cg_res, void* workspace, size_t workspace_bytes, void* stream) {
+    GF_CHECK_ARG(T >= 1 && n_obs >= 1 && n_images >= 1, "need at least one point, one observation and one image (each below 2^31)");
+    GF_CHECK_ARG(F >= 0 && F <= n_images, "need 0 <= F <= n_images");
+    GF_CHECK_ARG(iters >= 1 && iters <= BA_MAX_ITERS, "iters must be 1 .. 64");
+    GF_CHECK_ARG(thr > 0.f && thr < INFINITY, "thr must be positive and finite");
+    const char* bad = ba_pcg_check_limits(F, cg_iters, cg_tol);
+    GF_CHECK_ARG(bad == nullptr, bad);
+    GF_CHECK_ARG(obs_off_host && obs_image_host && img_off_host && img_obs_host && cam_free_host && obs_off && obs_image && obs_uv && img_off &&
+                 img_obs && cam_free && K && R_in && t_in && X_in && R_out && t_out && X_out && inliers && n_inliers && cost && accepted &&
+                 lambda && status && cg_used && cg_res, "null pointer");
+    bad = ba_check_tables(obs_off_host, T, n_obs, obs_image_host, img_off_host, img_obs_host, cam_free_host, n_images, F);
+    GF_CHECK_ARG(bad == nullptr, bad);
+    if (workspace == nullptr || workspace_bytes < gf_bundle_pcg_workspace_bytes(T, n_obs, n_images, F)) {
+        gf_set_error("gf_bundle_adjust_pcg: workspace too small");
+        return GF_ERR_WORKSPACE;
+    }
+    BaPcgArgs g;
+    ba_pcg_carve(g, workspace, T, n_obs, n_images, F);
+    BaArgs& a = g.a;
+    a.v.obs_off = obs_off; a.v.obs_image = obs_image; a.v.obs_uv = obs_uv; a.v.obs_point = a.obs_point; a.v.img_off = img_off;
+    a.v.img_obs = img_obs; a.v.cam_free = cam_free; a.v.cam_ok = a.cam_ok; a.v.K = K; a.v.T = T; a.v.n_obs = n_obs; a.v.n_images = n_images;
+    a.v.F = F; a.v.thr2 = (double)thr * (double)thr;
+    a.cam_free_in = cam_free;
+    a.R_in = R_in; a.t_in = t_in; a.X_in = X_in; a.R_out = R_out; a.t_out = t_out; a.X_out = X_out; a.inliers = inliers; a.n_inliers = n_inliers;
+    a.cost = cost; a.lambda = lambda; a.accepted = accepted; a.status = status;
+    g.cg_used = cg_used; g.cg_res = cg_res; g.tol2 = cg_tol * cg_tol;
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned g_all = (unsigned)(((long)(T > n_images ? T : n_images) + 255) / 256), g_pts = (unsigned)a.nb;
+    if (hipMemsetAsync(a.ctrl, 0, sizeof(BaCtrl), st) != hipSuccess || hipMemsetAsync(g.sc, 0, sizeof(BaPcgScalars), st) != hipSuccess ||
+        hipMemsetAsync(cg_used, 0, sizeof(int32_t) * (size_t)iters, st) != hipSuccess ||
+        hipMemsetAsync(cg_res, 0, sizeof(double) * (size_t)iters, st) != hipSuccess) {
+        gf_set_error("gf_bundle_adjust_pcg: hipMemsetAsync failed");
+        return GF_ERR_LAUNCH;
+    }
+    void* tok = gf_prof_begin("ba_init", st, (double)n_obs);
+    ba_init<<<g_all, 256, 0, st>>>(a);
+    ba_cost<<<g_pts, 256, 0, st>>>(a, 0);
+    ba_decide<<<1, 1, 0, st>>>(a, -1);
+    gf_prof_end("ba_init", tok, st);
+    for (int iter = 0; iter < iters; ++iter) {
+        tok = gf_prof_begin("ba_points", st, (double)n_obs);
+        ba_points<<<g_pts, 256, 0, st>>>(a);
+        gf_prof_end("ba_points", tok, st);
+        if (F > 0) {
+            tok = gf_prof_begin("ba_pcg_setup", st, (double)n_obs);
+            ba_pcg_setup<<<(unsigned)F, 256, 0, st>>>(g);
+            gf_prof_end("ba_pcg_setup", tok, st);
+            tok = gf_prof_begin("ba_pcg_step", st, (double)F);
+            ba_pcg_step<<<1, 256, 0, st>>>(g, iter, -1);
+            gf_prof_end("ba_pcg_step", tok, st);
+            for (int i = 0; i < cg_iters; ++i) {
+                tok = gf_prof_begin("ba_pcg_points", st, (double)n_obs);
+                ba_pcg_points<<<g_pts, 256, 0, st>>>(g);
+                gf_prof_end("ba_pcg_points", tok, st);
+                tok = gf_prof_begin("ba_pcg_cameras", st, (double)n_obs);
+                ba_pcg_cameras<<<(unsigned)F, 256, 0, st>>>(g);
+                gf_prof_end("ba_pcg_cameras", tok, st);
+                tok = gf_prof_begin("ba_pcg_step", st, (double)F);
+                ba_pcg_step<<<1, 256, 0, st>>>(g, iter, i);
+                gf_prof_end("ba_pcg_step", tok, st);
+            }
         }
         tok = gf_prof_begin("ba_update_cost", st, (double)n_obs);
         ba_update<<<g_all, 256, 0, st>>>(a);

@@ -856,6 +856,7 @@ class RefinedStructure(NamedTuple):
     cost: np.ndarray         # [stages * iters + stages] float64: the truncated cost before the first and after every iteration, per stage
     accepted: np.ndarray     # [stages * iters] int32: 1 where the iteration's step was taken
     n_free: int              # cameras that were free to move
+    cg_used: Optional[np.ndarray] = None  # solver='pcg': [stages * iters] int32, the CG iterations of every iteration; None for 'dense'
 
 
 def _refine_inputs(cm, tt, intrinsics, poses, fixed):
@@ -882,9 +883,9 @@ def _refine_inputs(cm, tt, intrinsics, poses, fixed):
                 uv=np.ascontiguousarray(kps[kp_off[obs_image].astype(np.int64) + obs_kp]), free=free, posed=posed)
 
 
-def _refine_device(a, thrs, iters, device):
-    """One upload, one ops.bundle_adjust per threshold (each from the state the one before left, all on the device), one read back ->
-    dict(R [n,9], t [n,3], X [T,3], inliers uint8 [N], cost, accepted) in numpy."""
+def _refine_device(a, thrs, iters, device, solver='dense', cg_iters=64, cg_tol=1e-6):
+    """One upload, one ops.bundle_adjust per threshold (each from the state the one before left, all on the device, all with the same
+    solver), one read back -> dict(R [n,9], t [n,3], X [T,3], inliers uint8 [N], cost, accepted; with solver='pcg' also cg_used) in numpy."""
     n, T, N = a['n'], len(a['X']), len(a['obs_image'])
     block = np.concatenate([x.reshape(-1).view(np.int32) for x in (np.ascontiguousarray(a['R']), np.ascontiguousarray(a['t']),
                                                                    np.ascontiguousarray(a['X']), a['K'], a['uv'], a['obs_off'], a['obs_image'],
@@ -902,18 +903,25 @@ def _refine_device(a, thrs, iters, device):
         K, uv = take(9 * n, torch.float32, n, 9), take(2 * N, torch.float32, N, 2)
         ooff, oimg, free = take(T + 1, torch.int32, T + 1), take(N, torch.int32, N), take(n, torch.int32, n)
         host = {'obs_off': a['obs_off'], 'obs_image': a['obs_image'], 'free': a['free']}
-        costs, accs = [], []
+        costs, accs, used = [], [], []
+        pcg = solver == 'pcg'
+        kw = dict(solver=solver, cg_iters=cg_iters, cg_tol=cg_tol) if pcg else {}
         for thr in thrs:
-            rs = ops.bundle_adjust(ooff, oimg, uv, K, R, t, X, free, thr=thr, iters=iters, host=host)
+            rs = ops.bundle_adjust(ooff, oimg, uv, K, R, t, X, free, thr=thr, iters=iters, host=host, **kw)
             R, t, X = rs['R'], rs['t'], rs['X']
             costs.append(rs['cost'])
             accs.append(rs['accepted'])
-        out = torch.cat([x.reshape(-1).view(torch.uint8) for x in (R, t, X, torch.cat(costs), torch.cat(accs), rs['inliers'])]).cpu().numpy()
+            used.append(rs['cg_used'] if pcg else rs['accepted'][:0])
+        out = torch.cat([x.reshape(-1).view(torch.uint8) for x in (R, t, X, torch.cat(costs), torch.cat(accs), torch.cat(used),
+                                                                   rs['inliers'])]).cpu().numpy()
     nc, na = len(thrs) * (iters + 1), len(thrs) * iters
-    cut = np.cumsum([0, 72 * n, 24 * n, 24 * T, 8 * nc, 4 * na])
+    cut = np.cumsum([0, 72 * n, 24 * n, 24 * T, 8 * nc, 4 * na, 4 * na if pcg else 0])
     f64 = lambda k: out[cut[k]:cut[k + 1]].view(np.float64)
-    return dict(R=f64(0).reshape(n, 9), t=f64(1).reshape(n, 3), X=f64(2).reshape(T, 3), cost=f64(3).copy(),
-                accepted=out[cut[4]:cut[5]].view(np.int32).copy(), inliers=out[cut[5]:].copy())
+    r = dict(R=f64(0).reshape(n, 9), t=f64(1).reshape(n, 3), X=f64(2).reshape(T, 3), cost=f64(3).copy(),
+             accepted=out[cut[4]:cut[5]].view(np.int32).copy(), inliers=out[cut[6]:].copy())
+    if pcg:
+        r['cg_used'] = out[cut[5]:cut[6]].view(np.int32).copy()
+    return r
 
 
 def _assemble_refined(cm, tt, poses, a, r, min_obs) -> RefinedStructure:
@@ -942,11 +950,12 @@ def _assemble_refined(cm, tt, poses, a, r, min_obs) -> RefinedStructure:
     for i, name in enumerate(cm.names):
         if a['free'][i]:
             out[name] = (R[i].copy(), t[i] - R[i] @ origin)             # t' = t + R origin
-    return RefinedStructure(out, tracks, np.asarray(r['cost']), np.asarray(r['accepted']), int(a['free'].sum()))
+    return RefinedStructure(out, tracks, np.asarray(r['cost']), np.asarray(r['accepted']), int(a['free'].sum()),
+                            np.asarray(r['cg_used']) if 'cg_used' in r else None)
 
 
 def refine(cm: ConsolidatedMatches, tt: TriangulatedTracks, intrinsics, poses, fixed=(), iters=16, thr=4.0, min_obs=2,
-           device='cuda') -> RefinedStructure:
+           device='cuda', solver='dense', cg_iters=64, cg_tol=1e-6) -> RefinedStructure:
     """Bundle adjustment on the device: the poses of the images of cm and the points of tt refined jointly, minimising the squared
     reprojection error of tt's observations truncated at thr pixels (ops.bundle_adjust; the rule is csrc/ba_spec.h: Levenberg-Marquardt,
     points eliminated by the Schur complement, dense Cholesky of the reduced camera system, `iters` iterations enqueued at once).  poses[name]
@@ -958,8 +967,19 @@ def refine(cm: ConsolidatedMatches, tt: TriangulatedTracks, intrinsics, poses, f
     Returns RefinedStructure: poses (a dict like the input), tracks (the layout of tt: only observations that are inliers at the final
     state, points with fewer than min_obs of them dropped, errors recomputed, point_of_keypoint rebuilt), cost, accepted, n_free.  The world
     origin is moved to the centre of the camera centres' bounding box before the upload and back afterwards, as in triangulate.  One upload,
-    one read back.  No intrinsics or distortion refinement, no robust loss other than the truncation, no re-triangulation inside the loop:
-    call triangulate again with the refined poses to win observations back."""
+    one read back.  solver='pcg' (csrc/ba_pcg_spec.h) solves the reduced camera system by matrix-free preconditioned conjugate gradients
+    instead of the dense Cholesky: up to 65536 free images (ops.BA_PCG_MAX_FREE), at most cg_iters (1 .. 256) CG iterations per iteration,
+    stopped at the relative tolerance cg_tol (in [0, 1)); every stage of a thr schedule uses the same solver, and the result's cg_used is
+    the log of CG iterations (None for 'dense').  The preconditioner is block Jacobi and the tolerance is fixed.  No intrinsics or
+    distortion refinement, no robust loss other than the truncation, no re-triangulation inside the loop: call triangulate again with the
+    refined poses to win observations back."""
+    if solver not in ('dense', 'pcg'):
+        raise ValueError(f"refine: solver must be 'dense' or 'pcg', not {solver!r}")
+    pcg = solver == 'pcg'
+    if pcg and not 1 <= int(cg_iters) <= ops.BA_PCG_MAX_ITERS:
+        raise ValueError(f'refine: cg_iters must be 1 .. {ops.BA_PCG_MAX_ITERS}')
+    if pcg and not 0.0 <= float(cg_tol) < 1.0:
+        raise ValueError('refine: cg_tol must be in [0, 1)')
     thrs = tuple(float(x) for x in (thr if isinstance(thr, (tuple, list, np.ndarray)) else (thr,)))
     if not thrs or not all(x > 0 and np.isfinite(x) for x in thrs):
         raise ValueError('refine: thr must be positive')
@@ -968,11 +988,17 @@ def refine(cm: ConsolidatedMatches, tt: TriangulatedTracks, intrinsics, poses, f
     if min_obs < 2:
         raise ValueError('refine: min_obs must be at least 2')
     a = _refine_inputs(cm, tt, intrinsics, poses, fixed)
-    if int(a['free'].sum()) > ops.BA_MAX_FREE:
+    if pcg and int(a['free'].sum()) > ops.BA_PCG_MAX_FREE:
+        raise ValueError(f"refine: {int(a['free'].sum())} free images, the limit is {ops.BA_PCG_MAX_FREE} with solver='pcg': name more "
+                         'images in fixed')
+    if not pcg and int(a['free'].sum()) > ops.BA_MAX_FREE:
         raise ValueError(f"refine: {int(a['free'].sum())} free images, the limit is {ops.BA_MAX_FREE} (the reduced camera system is solved "
-                         'densely): name more images in fixed')
+                         "densely): name more images in fixed, or pass solver='pcg'")
     if len(a['X']) == 0 or len(a['obs_image']) == 0:
-        return RefinedStructure(dict(poses), tt, np.zeros(0), np.zeros(0, np.int32), int(a['free'].sum()))
+        return RefinedStructure(dict(poses), tt, np.zeros(0), np.zeros(0, np.int32), int(a['free'].sum()), np.zeros(0, np.int32) if pcg else None)
+    if pcg:
+        return _assemble_refined(cm, tt, poses, a, _refine_device(a, thrs, int(iters), device, solver='pcg', cg_iters=int(cg_iters),
+                                                                  cg_tol=float(cg_tol)), min_obs)
     return _assemble_refined(cm, tt, poses, a, _refine_device(a, thrs, int(iters), device), min_obs)
 
 
@@ -1461,6 +1487,11 @@ def build_parser():
     rf.add_argument('--out', metavar='PTS2.npz', required=True, help='the refined points, in the format of `triangulate --out`')
     rf.add_argument('--out-poses', metavar='FILE2', required=True, help='all poses, the free ones refined, in the format of --poses')
     rf.add_argument('--device', default='cuda')
+    rf.add_argument('--solver', choices=('dense', 'pcg'), default='dense',
+                    help='the reduced camera system: dense Cholesky (at most 128 free images) or matrix-free preconditioned conjugate '
+                         'gradients (at most 65536)')
+    rf.add_argument('--cg-iters', type=int, default=64, help='--solver pcg: the cap of CG iterations per iteration (1 .. 256)')
+    rf.add_argument('--cg-tol', type=float, default=1e-6, help='--solver pcg: the relative tolerance at which CG stops, in [0, 1)')
     for p in (h, q, loc):
         p.add_argument('--cache-gb', type=float, default=None,
                        help='byte budget of the feature store in GB: least recently used images are dropped and extracted again when '
@@ -1554,7 +1585,8 @@ def run_refine(args):
                 q = line.strip()
                 if q and not q.startswith('#'):
                     fixed.append(q if q in cm.names else known.get(q if os.path.isabs(q) else os.path.normpath(os.path.join(fbase, q)), q))
-    rs = refine(cm, tt, intr, {nm: poses[nm] for nm in cm.names if nm in poses}, fixed, args.iters, args.thr, args.min_obs, device=args.device)
+    rs = refine(cm, tt, intr, {nm: poses[nm] for nm in cm.names if nm in poses}, fixed, args.iters, args.thr, args.min_obs, device=args.device,
+                solver=args.solver, cg_iters=args.cg_iters, cg_tol=args.cg_tol)
     write_triangulated(args.out, rs.tracks)
     write_poses(args.out_poses, rs.poses)
     print(f'{rs.n_free} free and {len(rs.poses) - rs.n_free} fixed images, {len(tt.points)} points, {len(tt.obs_image)} observations: cost '
@@ -1602,6 +1634,8 @@ def main(argv=None):
             ap.error('refine: --thr takes numbers separated by commas')
         if not 1 <= args.iters <= 64 or args.min_obs < 2 or not all(x > 0 for x in args.thr):
             ap.error('refine: need --iters 1 .. 64, --min-obs >= 2 and --thr > 0')
+        if args.solver == 'pcg' and not (1 <= args.cg_iters <= 256 and 0.0 <= args.cg_tol < 1.0):
+            ap.error('refine: need --cg-iters 1 .. 256 and 0 <= --cg-tol < 1')
         run_refine(args)
         return
     if args.cmd == 'localize-sparse':                                   # no model either: keypoints, matches and points in, poses out

@@ -1432,10 +1432,12 @@ def triangulate_tracks(track_off, obs_image, obs_uv, K, R, t, pixel_thr=4.0, min
 # ---------------------------------------------------------------------------------------------
 BA_MAX_FREE = 128               # ba_spec.h: the reduced camera system is dense, at most 768 x 768
 BA_MAX_ITERS = 64
+BA_PCG_MAX_FREE = 65536         # ba_pcg_spec.h: solver='pcg' never stores the reduced camera system
+BA_PCG_MAX_ITERS = 256
 BA_FLAG_STEP_FAILED, BA_FLAG_POINT_HELD, BA_FLAG_FREE_NO_POSE = 1, 2, 4     # bits of the status word
 
 
-def bundle_adjust(obs_off, obs_image, obs_uv, K, R, t, X, free, thr=4.0, iters=16, host=None):
+def bundle_adjust(obs_off, obs_image, obs_uv, K, R, t, X, free, thr=4.0, iters=16, host=None, solver='dense', cg_iters=64, cg_tol=1e-6):
     """Camera poses and 3-D points refined jointly on the device (csrc/ba_spec.h): Levenberg-Marquardt on the truncated squared
     reprojection error, the points eliminated by the Schur complement, the reduced camera system solved by a dense Cholesky.  Device
     tensors: obs_off int32 [T+1], obs_image int32 [N_obs], obs_uv fp32 [N_obs,2] (the observations of every point, as TriangulatedTracks
@@ -1445,8 +1447,20 @@ def bundle_adjust(obs_off, obs_image, obs_uv, K, R, t, X, free, thr=4.0, iters=1
     back from the device here.  More than 128 free cameras is a ValueError.  The image-major index of the observations is torch's stable
     sort.  Returns dict(R, t, X, inliers uint8 [N_obs] (takes part at the final state), n_inliers int32 [T], cost fp64 [iters+1] (never
     increases), accepted int32 [iters], lam fp64 [iters+1], status int32 [1] (BA_FLAG_* bits)).  All iterations are enqueued at once, the
-    decision to accept a step is taken on the device; no host synchronisation; bit-identical from run to run and to the host build."""
+    decision to accept a step is taken on the device; no host synchronisation; bit-identical from run to run and to the host build.
+    solver='pcg' (csrc/ba_pcg_spec.h): the reduced camera system is solved by matrix-free preconditioned conjugate gradients instead (block
+    Jacobi: the per-camera 6 x 6 blocks; at most cg_iters (1 .. 256) CG iterations per LM iteration, stopped once <r, M^-1 r> has fallen to
+    cg_tol^2 (0 <= cg_tol < 1) of its start; running out of iterations is no failure, the cost test judges the step).  It takes up to
+    BA_PCG_MAX_FREE (65536) free cameras, its workspace is O(N_obs + T + F), and the result gains cg_used int32 [iters] and cg_res fp64
+    [iters] (the CG iterations of every LM iteration and the last <r, M^-1 r> over its start)."""
     import numpy as np
+    if solver not in ('dense', 'pcg'):
+        raise ValueError(f"bundle_adjust: solver must be 'dense' or 'pcg', not {solver!r}")
+    pcg = solver == 'pcg'
+    if pcg and not 1 <= int(cg_iters) <= BA_PCG_MAX_ITERS:
+        raise ValueError(f'bundle_adjust: cg_iters must be 1 .. {BA_PCG_MAX_ITERS}')
+    if pcg and not 0.0 <= float(cg_tol) < 1.0:
+        raise ValueError('bundle_adjust: cg_tol must be in [0, 1)')
     _need_cuda(obs_off, obs_image, obs_uv)
     dev = obs_off.device
     T, n_obs = int(obs_off.numel()) - 1, int(obs_image.numel())
@@ -1470,7 +1484,9 @@ def bundle_adjust(obs_off, obs_image, obs_uv, K, R, t, X, free, thr=4.0, iters=1
     if free_h.size != n_images:
         raise ValueError(f'bundle_adjust: {n_images} images but {free_h.size} free flags')
     F = int(free_h.sum())
-    if F > BA_MAX_FREE:
+    if pcg and F > BA_PCG_MAX_FREE:
+        raise ValueError(f'bundle_adjust: {F} free cameras, the limit of solver=\'pcg\' is {BA_PCG_MAX_FREE}: fix more images')
+    if not pcg and F > BA_MAX_FREE:
         raise ValueError(f'bundle_adjust: {F} free cameras, the limit is {BA_MAX_FREE} (the reduced camera system is solved densely): fix more images')
     ooh, oop = _host_i32(host['obs_off'])
     oih, oip = _host_i32(host['obs_image'])
@@ -1495,6 +1511,16 @@ def bundle_adjust(obs_off, obs_image, obs_uv, K, R, t, X, free, thr=4.0, iters=1
     acc = torch.zeros(int(iters), dtype=torch.int32, device=dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     L_ = _lib.lib()
+    if pcg:
+        cg_used = torch.zeros(int(iters), dtype=torch.int32, device=dev)
+        cg_res = torch.zeros(int(iters), dtype=torch.float64, device=dev)
+        ws = _ws.get('bundle_adjust_pcg', L_.gf_bundle_pcg_workspace_bytes(T, n_obs, n_images, F), dev)
+        check(L_.gf_bundle_adjust_pcg(oop, oip, ifp, iop, cfp, _p(toff), T, n_obs, _p(oimg), _p(ouv), _p(img_off), _p(img_obs), _p(cam_free), n_images,
+                                      F, _p(Kt), _p(Rt), _p(tt), _p(Xt), float(thr), int(iters), int(cg_iters), float(cg_tol), _p(Ro), _p(to), _p(Xo),
+                                      _p(inl), _p(nin), _p(cost), _p(acc), _p(lam), _p(status), _p(cg_used), _p(cg_res), _p(ws), ws.numel(),
+                                      _stream()), 'gf_bundle_adjust_pcg')
+        return {'R': Ro.view(n_images, 3, 3), 't': to, 'X': Xo, 'inliers': inl, 'n_inliers': nin, 'cost': cost, 'accepted': acc, 'lam': lam,
+                'status': status, 'cg_used': cg_used, 'cg_res': cg_res}
     ws = _ws.get('bundle_adjust', L_.gf_bundle_workspace_bytes(T, n_obs, n_images, F), dev)
     check(L_.gf_bundle_adjust(oop, oip, ifp, iop, cfp, _p(toff), T, n_obs, _p(oimg), _p(ouv), _p(img_off), _p(img_obs), _p(cam_free), n_images, F,
                               _p(Kt), _p(Rt), _p(tt), _p(Xt), float(thr), int(iters), _p(Ro), _p(to), _p(Xo), _p(inl), _p(nin), _p(cost), _p(acc),

@@ -41,7 +41,7 @@ typedef enum { GF_F32 = 0, GF_F16 = 1, GF_BF16 = 2 } gf_dtype;
  * the end change no existing one; a binding that needs them fails at load on the missing symbol (geoformer_amd/_lib.py binds every name).
  * Likewise with the gf_keypoint_* entries, gf_fundamental_* (gf_fundamental_ransac_lo and its workspace query included), gf_linear_rows,
  * gf_index_rows, gf_fine_rows*, gf_abspose_* and gf_xyz_lookup (with gf_xyz_map), gf_track_link, gf_track_flatten and gf_triangulate*,
- * gf_covis_cluster, gf_sparse_rows and gf_covis_select, gf_bundle_workspace_bytes and gf_bundle_adjust. */
+ * gf_covis_cluster, gf_sparse_rows and gf_covis_select, gf_bundle_workspace_bytes and gf_bundle_adjust, gf_bundle_pcg_workspace_bytes and gf_bundle_adjust_pcg. */
 #define GF_ABI_VERSION 4
 int gf_abi_version(void);
 const char* gf_last_error(void);
@@ -915,6 +915,29 @@ int gf_bundle_adjust(const int32_t* obs_off_host, const int32_t* obs_image_host,
                      const double* R_in, const double* t_in, const double* X_in, float thr, int iters, double* R_out, double* t_out,
                      double* X_out, uint8_t* inliers, int32_t* n_inliers, double* cost, int32_t* accepted, double* lambda, int32_t* status,
                      void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Bundle adjustment beyond 128 free cameras: the same Levenberg-Marquardt shell, the reduced camera system solved by matrix-free
+ * preconditioned conjugate gradients (block-Jacobi preconditioner: the per-camera 6 x 6 blocks) instead of the dense Cholesky.  The rule
+ * is geoformer_amd/csrc/ba_pcg_spec.h; the system matrix is never stored, the workspace is O(n_obs + T + F).  Bit-exact against the host
+ * build (gf_ba_host_adjust_pcg in csrc/host/ba_host.cpp) and from run to run.
+ *   gf_bundle_adjust_pcg
+ *     The arguments of gf_bundle_adjust, and: 1 <= cg_iters <= 256 (the cap of CG iterations per LM iteration; running out is no failure,
+ *     the cost test judges the step), 0 <= cg_tol < 1 and finite (CG stops once <r, M^-1 r> <= cg_tol^2 times its start), F <= 65536:
+ *     anything else is GF_ERR_INVALID_ARGUMENT.  Further outputs: cg_used int32 [iters] (CG iterations completed in each LM iteration),
+ *     cg_res fp64 [iters] (the last <r, M^-1 r> over its start; 1 before the first CG iteration completes, 0 when the right-hand side is 0
+ *     or F = 0).  Status bit 1 also covers a PCG breakdown (a camera block that cannot be inverted, <p, S p> not positive).
+ *     workspace: gf_bundle_pcg_workspace_bytes(T, n_obs, n_images, F) bytes (0 for arguments the entry point rejects).  All LM and CG
+ *     iterations are enqueued at once; once a solve has stopped, its remaining launches return at once.  No host synchronisation.
+ * ------------------------------------------------------------------------------------------ */
+size_t gf_bundle_pcg_workspace_bytes(int T, int n_obs, int n_images, int F);
+int gf_bundle_adjust_pcg(const int32_t* obs_off_host, const int32_t* obs_image_host, const int32_t* img_off_host, const int32_t* img_obs_host,
+                         const int32_t* cam_free_host, const int32_t* obs_off, int T, int n_obs, const int32_t* obs_image, const float* obs_uv,
+                         const int32_t* img_off, const int32_t* img_obs, const int32_t* cam_free, int n_images, int F, const float* K,
+                         const double* R_in, const double* t_in, const double* X_in, float thr, int iters, int cg_iters, double cg_tol,
+                         double* R_out, double* t_out, double* X_out, uint8_t* inliers, int32_t* n_inliers, double* cost, int32_t* accepted,
+                         double* lambda, int32_t* status, int32_t* cg_used, double* cg_res, void* workspace, size_t workspace_bytes,
+                         void* stream);
 
 #ifdef __cplusplus
 }
