@@ -28,6 +28,7 @@ ABSPOSE_HOST_LIB = os.path.join(OBJ, 'libabspose_host.so')
 TRI_HOST_LIB = os.path.join(OBJ, 'libtri_host.so')
 COVIS_HOST_LIB = os.path.join(OBJ, 'libcovis_host.so')
 BA_HOST_LIB = os.path.join(OBJ, 'libba_host.so')
+CAMERA_HOST_LIB = os.path.join(OBJ, 'libcamera_host.so')
 
 
 def _headers_digest():
@@ -140,8 +141,16 @@ def build_ba_host(verbose=True):
                                                                  'keypoint_spec.h', 'gf_hash.h')), verbose)
 
 
+def build_camera_host(verbose=True):
+    """TEST INFRASTRUCTURE and CPU reference: the serial host form of the lens-distortion rule (csrc/host/camera_host.cpp over
+    csrc/camera_spec.h, the text k_camera.hip compiles for the device).  Only tests and tools/camera_probe.py load it."""
+    return _build_host_lib(CAMERA_HOST_LIB, 'camera_host.stamp', os.path.join(CSRC, 'host', 'camera_host.cpp'),
+                           (os.path.join(CSRC, 'camera_spec.h'),), verbose)
+
+
 def build(verbose=True, jobs=4):
     os.makedirs(OBJ, exist_ok=True)
+    build_camera_host(verbose)
     build_pose_host(verbose)
     build_warp_host(verbose)
     build_keypoint_host(verbose)

@@ -16,6 +16,7 @@ output.  The homography of the HPatches metric is estimated from the fine matche
 """
 import collections
 import glob
+import math
 import os
 import threading
 import time
@@ -594,7 +595,8 @@ def localize_queries(pairs, results, intrinsics, xyz_maps, thr=12.0, min_inliers
     (ops.xyz_lookup), all pairs of a query form one problem in pair order, and one absolute-pose RANSAC per query follows
     (ops.ransac_absolute_pose: P3P hypotheses, reprojection error below thr pixels; the rule is csrc/abs_solver.h) - one upload, the
     lookup, three launches (four with refit) for all queries, one read back.  localized[q] = a model was found and n_inliers[q] >=
-    min_inliers.  No covisibility clustering, no distortion parameters."""
+    min_inliers.  No covisibility clustering; no distortion parameters here: undistort_results removes lens distortion from the matches
+    beforehand."""
     if len(pairs) != len(results):
         raise ValueError(f'localize_queries: {len(pairs)} pairs but {len(results)} results')
     P = len(results)
@@ -692,6 +694,184 @@ def read_intrinsics(path):
     return out
 
 
+def write_intrinsics(path, intrinsics, names=None):
+    """The inverse of read_intrinsics: one line `name fx fy cx cy` per entry of `names` (default: every key), names as they are."""
+    with open(path, 'w') as f:
+        for name in (intrinsics if names is None else names):
+            K = np.asarray(intrinsics[name], dtype=np.float64)
+            f.write(' '.join([name] + [repr(float(v)) for v in (K[0, 0], K[1, 1], K[0, 2], K[1, 2])]) + '\n')
+
+
+# ---------------------------------------------------------------------------------------------
+# lens distortion: the match coordinates of real cameras are undistorted once, on the device, before any geometry runs
+# ---------------------------------------------------------------------------------------------
+CAMERA_MODELS = {'SIMPLE_PINHOLE': 3, 'PINHOLE': 4, 'SIMPLE_RADIAL': 4, 'RADIAL': 5, 'OPENCV': 8}     # COLMAP's names -> number of parameters
+
+
+class Camera(NamedTuple):
+    model: str               # a key of CAMERA_MODELS
+    width: int
+    height: int
+    params: tuple            # COLMAP's order: f | fx fy, then cx cy, then the model's distortion terms
+
+
+def canonical_camera(camera):
+    """The canonical record (fx, fy, cx, cy, k1, k2, p1, p2) of csrc/camera_spec.h for a Camera of any supported model."""
+    model, p = camera.model, tuple(float(v) for v in camera.params)
+    if model not in CAMERA_MODELS:
+        raise ValueError(f'camera model {model!r} is not supported (supported: {", ".join(CAMERA_MODELS)})')
+    if len(p) != CAMERA_MODELS[model]:
+        raise ValueError(f'{model} takes {CAMERA_MODELS[model]} parameters, got {len(p)}')
+    if model in ('PINHOLE', 'OPENCV'):
+        return p + (0.0,) * (8 - len(p))
+    return (p[0], p[0], p[1], p[2]) + p[3:] + (0.0,) * (7 - len(p))
+
+
+def read_cameras(path):
+    """hloc's query-list lines: `path MODEL W H params...` with COLMAP's model names and parameter order (SIMPLE_PINHOLE f cx cy; PINHOLE
+    fx fy cx cy; SIMPLE_RADIAL f cx cy k; RADIAL f cx cy k1 k2; OPENCV fx fy cx cy k1 k2 p1 p2).  Blank lines and '#' lines are skipped; a
+    relative path is relative to the file -> {path: Camera}.  An unknown model, a wrong number of parameters, a value that is not finite
+    or a focal length that is not positive is a ValueError naming file and line."""
+    base = os.path.dirname(os.path.abspath(path))
+    out = {}
+    with open(path) as f:
+        for no, line in enumerate(f, 1):
+            parts = line.split()
+            if not parts or parts[0].startswith('#'):
+                continue
+            if len(parts) < 4:
+                raise ValueError(f'{path}:{no}: expected `path MODEL W H params...`, got {len(parts)} fields')
+            model = parts[1]
+            if model not in CAMERA_MODELS:
+                raise ValueError(f'{path}:{no}: unknown camera model {model!r} (supported: {", ".join(CAMERA_MODELS)})')
+            if len(parts) - 4 != CAMERA_MODELS[model]:
+                raise ValueError(f'{path}:{no}: {model} takes {CAMERA_MODELS[model]} parameters, got {len(parts) - 4}')
+            try:
+                w, h = int(parts[2]), int(parts[3])
+                params = tuple(float(v) for v in parts[4:])
+            except ValueError:
+                raise ValueError(f'{path}:{no}: W and H must be integers and the parameters numbers') from None
+            if not all(math.isfinite(v) for v in params):
+                raise ValueError(f'{path}:{no}: a parameter that is not finite')
+            if not all(v > 0 for v in params[:2 if model in ('PINHOLE', 'OPENCV') else 1]):
+                raise ValueError(f'{path}:{no}: a focal length that is not positive')
+            name = parts[0] if os.path.isabs(parts[0]) else os.path.normpath(os.path.join(base, parts[0]))
+            out[name] = Camera(model, w, h, params)
+    return out
+
+
+def write_cameras(path, cameras):
+    """The inverse of read_cameras: one line per camera; a name under the file's directory is written relative to it."""
+    base = os.path.dirname(os.path.abspath(path))
+    with open(path, 'w') as f:
+        for name, cam in cameras.items():
+            canonical_camera(cam)                                          # (the model and its parameter count)
+            full = os.path.abspath(name)
+            shown = os.path.relpath(full, base) if full.startswith(base + os.sep) else full
+            f.write(' '.join([shown, cam.model, str(int(cam.width)), str(int(cam.height))] + [repr(float(v)) for v in cam.params]) + '\n')
+
+
+def pinhole_of(cameras):
+    """{name: Camera} -> {name: 3 x 3 K}: the intrinsics that hold for undistorted coordinates (what read_intrinsics returns)."""
+    out = {}
+    for name, cam in cameras.items():
+        fx, fy, cx, cy = canonical_camera(cam)[:4]
+        out[name] = np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1.0]])
+    return out
+
+
+class UndistortedResults(list):
+    """The list undistort_results returns, with n_failed int32 [P] (rows of a pair with a side that has no pre-image) and status (per
+    pair: uint8 [n_p, 2], the status byte of each side of each row: 0 fine, 1 non-finite input, 2 no pre-image)."""
+    n_failed = None
+    status = None
+
+
+def _original_pixel_rows(results):
+    """[n, 4] float32 matches in the pixels of the original images for either return convention of match_many: the four-element tuple
+    holds them, the five-element one (no_match_upscale) holds resized coordinates and, as element 4, the factors that scale them back."""
+    return [np.ascontiguousarray((np.asarray(r[0], dtype=np.float64).reshape(-1, 4) * np.asarray(r[4], dtype=np.float64).reshape(1, 4)
+                                  if len(r) > 4 else np.asarray(r[0])).astype(np.float32).reshape(-1, 4)) for r in results]
+
+
+def undistort_results(pairs, results, cameras, device='cuda'):
+    """[(path0, path1), ...], the tuples match_many returned for them (either return convention) and {path: Camera} -> (results',
+    intrinsics): the same tuples with every coordinate replaced by the pixel of an ideal pinhole camera with the same fx, fy, cx, cy, and
+    {path: 3 x 3 K} of those cameras (pinhole_of) - what verify_matches, consolidate_matches, localize_queries, triangulate, refine and
+    localize_queries_sparse take, unchanged.  The rule is csrc/camera_spec.h (COLMAP's SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL,
+    OPENCV; a guarded Newton iteration in fp64): one upload of all rows, one launch per side (ops.undistort_points reads the two sides of
+    the [M, 4] block in place), one read back.  Scores are untouched; matches, kpts1 and kpts2 come back as float32.  A row with a side
+    that has no pre-image (the pixel lies beyond the model's range) or a non-finite coordinate is NaN on that side: the stages downstream
+    drop such rows.  results'.n_failed counts them per pair, results'.status holds the status bytes.
+    Camera parameters refer to the original image, so the coordinates of a no_match_upscale tuple are first scaled back by its element 4;
+    the tuple returned for it holds original-image coordinates and ones as element 4.
+    Every image of `pairs` needs an entry in `cameras`, else ValueError.  Thresholds downstream are then in ideal-pinhole pixels, which
+    are stretched towards the corners under barrel distortion."""
+    pairs = [tuple(p) for p in pairs]
+    if len(pairs) != len(results):
+        raise ValueError(f'undistort_results: {len(pairs)} pairs but {len(results)} results')
+    index = {}
+    pim = np.array([[index.setdefault(path, len(index)) for path in p] for p in pairs], np.int32).reshape(-1, 2)
+    missing = [n for n in index if n not in cameras]
+    if missing:
+        raise ValueError(f'undistort_results: no camera for {missing[0]!r}')
+    names = list(index)
+    intrinsics = pinhole_of({n: cameras[n] for n in names})
+    ms = _original_pixel_rows(results)
+    P = len(pairs)
+    offsets = np.concatenate([[0], np.cumsum([len(m) for m in ms])]).astype(np.int32)
+    M = int(offsets[-1])
+    out = UndistortedResults()
+    if M:
+        table = np.array([canonical_camera(cameras[n]) for n in names], dtype=np.float64)
+        C = len(names)
+        # one upload: the camera table first (64-bit words), then everything else as 32-bit words
+        block = np.concatenate([a.reshape(-1).view(np.int32) for a in (table, *ms, offsets, np.ascontiguousarray(pim[:, 0]),
+                                                                       np.ascontiguousarray(pim[:, 1]))])
+        with torch.cuda.device(device):
+            d = torch.from_numpy(block).to(device)
+            o = 16 * C
+            tab = d[:o].view(torch.float64).view(C, 8)
+            rows = d[o:o + 4 * M].view(torch.float32).view(M, 4)
+            off = d[o + 4 * M:o + 4 * M + P + 1]
+            cam = d[o + 4 * M + P + 1:].view(2, P)
+            res = torch.empty(2, M, 2, dtype=torch.float32, device=d.device)
+            flags = torch.zeros(2, dtype=torch.int32, device=d.device)
+            st = [ops.undistort_points(rows[:, 2 * s:2 * s + 2], off, cam[s], tab, out=res[s], flags=flags)[1] for s in (0, 1)]
+            back = torch.cat([res.view(-1).view(torch.uint8), flags.view(torch.uint8), *st]).cpu().numpy()      # the one read back
+        ops.raise_camera_flags('undistort_results', back[16 * M:16 * M + 8].view(np.int32))
+        xy = back[:16 * M].view(np.float32).reshape(2, M, 2)
+        status = back[16 * M + 8:].reshape(2, M)
+    else:
+        xy, status = np.zeros((2, 0, 2), np.float32), np.zeros((2, 0), np.uint8)
+    out.status, failed = [], []
+    for p, r in enumerate(results):
+        b, e = int(offsets[p]), int(offsets[p + 1])
+        k0, k1 = xy[0, b:e].copy(), xy[1, b:e].copy()
+        m = np.concatenate([k0, k1], axis=1)
+        out.append((m, k0, k1, r[3], np.ones(4)) if len(r) > 4 else (m, k0, k1, r[3]))
+        s = np.ascontiguousarray(status[:, b:e].T)
+        out.status.append(s)
+        failed.append(int((s == ops.CM_ST_NO_PREIMAGE).any(axis=1).sum()))
+    out.n_failed = np.array(failed, np.int32)
+    return out, intrinsics
+
+
+def undistort_points(points, camera, device='cuda'):
+    """[n, 2] pixels of one Camera -> (float32 [n, 2] pixels of the ideal pinhole camera with its fx, fy, cx, cy, uint8 [n] status as in
+    undistort_results) - for the point lists of estimate_relative_pose and estimate_absolute_pose, with K = pinhole_of's."""
+    pts = np.ascontiguousarray(np.asarray(points, dtype=np.float32).reshape(-1, 2))
+    n = len(pts)
+    if n == 0:
+        canonical_camera(camera)
+        return np.zeros((0, 2), np.float32), np.zeros(0, np.uint8)
+    with torch.cuda.device(device):
+        tab = ops.camera_table([canonical_camera(camera)], device)
+        seg = torch.tensor([0, n, 0], dtype=torch.int32).to(device)
+        out, st = ops.undistort_points(torch.from_numpy(pts).to(device), seg[:2], seg[2:], tab)
+        return out.cpu().numpy(), st.cpu().numpy()
+
+
 def write_consolidated(out_dir, cm: ConsolidatedMatches):
     """names.txt (one image path per line, line i = image i), keypoints.npz (k00000, ...: [K_i, 2] float32 per image) and matches.npz
     (pairs [P, 2] int32 image indices; m00000, ...: [n_p, 2] int32 keypoint indices per pair)."""
@@ -767,7 +947,8 @@ def triangulate(cm: ConsolidatedMatches, intrinsics, poses, thr=4.0, min_angle=1
     on its inliers up to `refit` times (ops.triangulate_tracks; the rule is csrc/tri_solver.h), and is kept with at least min_obs
     inliers.  refit defaults to 2 here (0 in ops): a two-ray midpoint alone is a poor point for a long track.  Before the upload the world
     origin is moved to the centre of the bounding box of the camera centres (fp64), and the points are moved back afterwards.  One upload,
-    one read back.  No bundle adjustment, no re-triangulation or merging of tracks, no splitting of conflict tracks, no distortion."""
+    one read back.  No bundle adjustment, no re-triangulation or merging of tracks, no splitting of conflict tracks; no distortion
+    here: undistort_results removes it from the matches before they are consolidated."""
     n, kp_off, K, R, t, origin, ids, id_off, kps, pim = _triangulation_inputs(cm, intrinsics, poses)
     n_nodes, P, E = int(kp_off[-1]), len(cm.matches), len(ids)
     empty = _assemble_tracks(n, kp_off, 0, *([np.zeros(0)] * 4), np.zeros(1, np.int32), *([np.zeros(0, np.int32)] * 2), np.zeros(0, bool), origin)
@@ -1419,6 +1600,12 @@ def build_parser():
     q.add_argument('--qt-dthres', type=float, default=4, help='with --keypoints: keypoints of a cell closer than this are merged')
     q.add_argument('--no-qt-unique', dest='qt_unique', action='store_false',
                    help='with --keypoints: keep every match of a merged keypoint instead of its best one per pair')
+    q.add_argument('--cameras', metavar='FILE', default=None,
+                   help='one line per image: path MODEL W H params... (COLMAP\'s SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV; the '
+                        'parameters refer to the original image).  The matches are undistorted on the device right after matching: every '
+                        'coordinate written (--out, --keypoints, --verify) is then a pixel of the ideal pinhole camera with the same fx fy cx cy '
+                        '(of the original image, also under --no-match-upscale), and --keypoints DIR also gets intrinsics.txt for `triangulate`, '
+                        '`refine` and `localize-sparse`')
     q.add_argument('--verify', action='store_true',
                    help='verify every pair geometrically (fundamental-matrix RANSAC on the device, no intrinsics needed): each .npz of --out gains '
                         'F, inliers and verified; with --keypoints only the inliers of verified pairs are consolidated and two_view.npz is written')
@@ -1432,7 +1619,12 @@ def build_parser():
     loc.add_argument('--xyz', metavar='DIR', required=True,
                      help="the 3-D map of a database image: DIR/<its path relative to the list>.npy, float32 [H, W, 3] in the coordinates of "
                           'its keypoints (the original image unless --no-match-upscale), NaN where a pixel has no 3-D point')
-    loc.add_argument('--intrinsics', metavar='FILE', required=True, help='one line per query: path fx fy cx cy')
+    cam = loc.add_mutually_exclusive_group(required=True)
+    cam.add_argument('--intrinsics', metavar='FILE', default=None, help='one line per query: path fx fy cx cy')
+    cam.add_argument('--cameras', metavar='FILE', default=None,
+                     help='instead of --intrinsics: one line per image, queries and database images alike: path MODEL W H params... (as `pairs '
+                          '--cameras`).  The matches are undistorted on the device right after matching; the 3-D maps are then looked up at '
+                          'ideal-pinhole coordinates of the database images')
     loc.add_argument('--out', default=None, help='file with one line per localised query: path qw qx qy qz tx ty tz (x_cam = R X + t)')
     loc.add_argument('--thr', type=float, default=12.0, help='inlier threshold, reprojection error in pixels')
     loc.add_argument('--min-inliers', type=int, default=12, help='a query with fewer inliers is not localised')
@@ -1618,6 +1810,18 @@ def run_triangulate(args):
     return tt
 
 
+def _cameras_for(path, pairs):
+    """read_cameras(path) keyed by the image names of `pairs`: a name is looked up as the pair list has it, then as an absolute path."""
+    cams = read_cameras(path)
+    out = {}
+    for name in {n for p in pairs for n in p}:
+        full = os.path.abspath(name)
+        if name not in cams and full not in cams:
+            raise SystemExit(f'{path}: no camera for {name!r}')
+        out[name] = cams[name] if name in cams else cams[full]
+    return out
+
+
 def main(argv=None):
     """`python -m geoformer_amd.matcher match|hpatches|pairs|localize|triangulate|refine|localize-sparse ...` (arguments: build_parser)."""
     ap = build_parser()
@@ -1659,6 +1863,11 @@ def main(argv=None):
     if args.cmd == 'pairs':
         pairs = read_pair_list(args.list) if args.list is not None else all_pairs(args.all_pairs)
         results = matcher.match_many(pairs, batch=args.batch, pad=args.pad, max_waste=args.pad_waste)
+        intr = None
+        if args.cameras:
+            results, intr = undistort_results(pairs, results, _cameras_for(args.cameras, pairs), device=matcher.device)
+            print(f'{args.cameras}: {sum(len(r[0]) for r in results)} matches undistorted, {int(results.n_failed.sum())} with a side beyond its '
+                  f"camera model's range (dropped downstream)")
         vm = (verify_matches(pairs, results, args.verify_thr, args.min_inliers, args.sc_thres, device=matcher.device, refit=args.verify_refit)
               if args.verify else None)
         refit = {} if vm is None or not args.verify_refit else {'refit_rounds': vm.rounds}
@@ -1677,6 +1886,8 @@ def main(argv=None):
             cm = consolidate_matches(pairs, results, args.sc_thres, args.qt_psize, args.qt_dthres, args.qt_unique, device=matcher.device,
                                      keep=None if vm is None else vm.masks)
             write_consolidated(args.keypoints, cm)
+            if intr is not None:
+                write_intrinsics(os.path.join(args.keypoints, 'intrinsics.txt'), intr, cm.names)
             if vm is not None:
                 np.savez(os.path.join(args.keypoints, 'two_view.npz'), pairs=cm.pair_images, F=vm.F, n_inliers=vm.n_inliers, verified=vm.verified, **refit)
             print(f'{len(cm.names)} images, {sum(len(k) for k in cm.keypoints)} keypoints, {sum(len(m) for m in cm.matches)} matches as keypoint '
@@ -1688,7 +1899,11 @@ def main(argv=None):
         base = os.path.dirname(os.path.abspath(args.list))
         results = matcher.match_many(pairs, batch=args.batch, pad=args.pad, max_waste=args.pad_waste)
         xyz = {d: os.path.join(args.xyz, os.path.relpath(d, base) + '.npy') for _, d in pairs}
-        lq = localize_queries(pairs, results, read_intrinsics(args.intrinsics), xyz, args.thr, args.min_inliers, args.sc_thres,
+        if args.cameras:
+            results, intr = undistort_results(pairs, results, _cameras_for(args.cameras, pairs), device=matcher.device)
+        else:
+            intr = read_intrinsics(args.intrinsics)
+        lq = localize_queries(pairs, results, intr, xyz, args.thr, args.min_inliers, args.sc_thres,
                               device=matcher.device, refit=args.refit)
         if args.out:
             with open(args.out, 'w') as f:

@@ -651,6 +651,72 @@ def xyz_lookup(table, pair_offsets, pts, pts_stride=None):
     return out
 
 
+CM_ST_OK, CM_ST_NONFINITE, CM_ST_NO_PREIMAGE, CM_ST_ARGS = 0, 1, 2, 3      # camera_spec.h CM_ST_*: the status byte of a point
+
+
+def camera_table(records, device):
+    """The device table of undistort_points / distort_points for a list of canonical camera records (fx, fy, cx, cy, k1, k2, p1, p2;
+    csrc/camera_spec.h, matcher.canonical_camera makes them) -> fp64 [C, 8] tensor."""
+    recs = [tuple(float(v) for v in r) for r in records]
+    if any(len(r) != 8 for r in recs):
+        raise ValueError('camera_table: a canonical record has 8 values: fx, fy, cx, cy, k1, k2, p1, p2')
+    return torch.tensor(recs, dtype=torch.float64).reshape(-1, 8).to(device)
+
+
+def _camera_points(entry, pts, seg_offsets, seg_camera, cameras, pts_stride, out, want_status, flags):
+    _need_cuda(pts, seg_offsets, seg_camera, cameras)
+    dev = pts.device
+    P, S, C = pts.shape[0], seg_camera.numel(), cameras.shape[0]
+    if out is None:
+        out = torch.empty(P, 2, dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (P, 2) or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f'{entry}: out must be a contiguous fp32 [{P}, 2] tensor on the device of pts')
+    status = torch.empty(P, dtype=torch.uint8, device=dev) if want_status else None
+    if pts.dtype != torch.float32 or (P and pts.stride(-1) != 1):
+        raise ValueError(f'{entry}: pts must be fp32 with unit stride along a row')
+    if cameras.dtype != torch.float64 or cameras.dim() != 2 or cameras.shape[1] != 8 or not cameras.is_contiguous():
+        raise ValueError(f'{entry}: cameras must be a contiguous fp64 [C, 8] tensor (ops.camera_table)')
+    stride = (int(pts.stride(0)) if P else 2) if pts_stride is None else int(pts_stride)
+    off = _contig(seg_offsets.to(device=dev, dtype=torch.int32))
+    cam = _contig(seg_camera.to(device=dev, dtype=torch.int32))
+    if off.numel() != S + 1:
+        raise ValueError(f'{entry}: seg_offsets has {off.numel()} entries for {S} segments')
+    own = flags is None
+    if own:
+        flags = torch.zeros(2, dtype=torch.int32, device=dev)
+    check(getattr(_lib.lib(), entry)(_p(pts), stride, P, _p(off), _p(cam), S, _p(cameras), C, _p(out), _p(status), _p(flags), _stream()), entry)
+    if own and P:
+        raise_camera_flags(entry, flags.cpu())
+    return out, status
+
+
+def raise_camera_flags(what, flags):
+    """flags: the two flag words of gf_undistort_points / gf_distort_points on the host."""
+    if int(flags[0]):
+        raise ValueError(f'{what}: seg_offsets is not an ascending list from 0 to the number of points')
+    if int(flags[1]):
+        raise ValueError(f'{what}: a segment names a camera outside the table')
+
+
+def undistort_points(pts, seg_offsets, seg_camera, cameras, pts_stride=None, out=None, flags=None):
+    """Pixels of real cameras -> pixels of an ideal pinhole camera with the same fx, fy, cx, cy (csrc/camera_spec.h), one launch.  pts
+    fp32 [P, 2] (x, y) - or any fp32 tensor whose row i starts pts_stride floats after row i - 1, as the columns 0:2 or 2:4 of a match
+    block, read in place; seg_offsets int32 [S+1] and seg_camera int32 [S] on the device cut the rows into segments of one camera each;
+    cameras from camera_table.  Returns (out fp32 [P, 2], status uint8 [P]): status 0 fine, 1 non-finite input, 2 no pre-image found (the
+    pixel lies beyond the model's range), 3 the row has no segment or camera; on status != 0 the row of out is NaN - the stages downstream
+    drop such rows.  A camera without distortion passes the input bits through.
+    Offsets that do not ascend from 0 to P and a camera index outside the table raise ValueError after one device-to-host read of two
+    flag words; nothing wraps.  flags = an int32 [2] device tensor of zeros: no read here, the caller looks at it (raise_camera_flags)
+    with a read of its own."""
+    return _camera_points('gf_undistort_points', pts, seg_offsets, seg_camera, cameras, pts_stride, out, True, flags)
+
+
+def distort_points(pts, seg_offsets, seg_camera, cameras, pts_stride=None, out=None, flags=None):
+    """The inverse of undistort_points in closed form: pixels of the ideal pinhole camera -> pixels of the real image, for drawing matches
+    on the images and for round trips.  Same arguments; returns out fp32 [P, 2] (NaN for a non-finite row)."""
+    return _camera_points('gf_distort_points', pts, seg_offsets, seg_camera, cameras, pts_stride, out, False, flags)[0]
+
+
 def epipolar_errors(mkpts0, mkpts1, m_bids, T_0to1, K0, K1):
     """Squared symmetric epipolar distance of every match under E = [t]x R of its pair's T_0to1 (metrics.py:30-69), fp32 [M]."""
     _need_cuda(mkpts0, mkpts1, m_bids, T_0to1)

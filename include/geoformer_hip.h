@@ -41,7 +41,8 @@ typedef enum { GF_F32 = 0, GF_F16 = 1, GF_BF16 = 2 } gf_dtype;
  * the end change no existing one; a binding that needs them fails at load on the missing symbol (geoformer_amd/_lib.py binds every name).
  * Likewise with the gf_keypoint_* entries, gf_fundamental_* (gf_fundamental_ransac_lo and its workspace query included), gf_linear_rows,
  * gf_index_rows, gf_fine_rows*, gf_abspose_* and gf_xyz_lookup (with gf_xyz_map), gf_track_link, gf_track_flatten and gf_triangulate*,
- * gf_covis_cluster, gf_sparse_rows and gf_covis_select, gf_bundle_workspace_bytes and gf_bundle_adjust, gf_bundle_pcg_workspace_bytes and gf_bundle_adjust_pcg. */
+ * gf_covis_cluster, gf_sparse_rows and gf_covis_select, gf_bundle_workspace_bytes and gf_bundle_adjust, gf_bundle_pcg_workspace_bytes and gf_bundle_adjust_pcg,
+ * gf_undistort_points and gf_distort_points. */
 #define GF_ABI_VERSION 4
 int gf_abi_version(void);
 const char* gf_last_error(void);
@@ -938,6 +939,28 @@ int gf_bundle_adjust_pcg(const int32_t* obs_off_host, const int32_t* obs_image_h
                          double* R_out, double* t_out, double* X_out, uint8_t* inliers, int32_t* n_inliers, double* cost, int32_t* accepted,
                          double* lambda, int32_t* status, int32_t* cg_used, double* cg_res, void* workspace, size_t workspace_bytes,
                          void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Lens distortion: match coordinates of real cameras -> pixels of an ideal pinhole camera with the same fx, fy, cx, cy, once, before any
+ * geometry runs (what COLMAP's estimators do with their image points).  The rule is geoformer_amd/csrc/camera_spec.h: COLMAP's
+ * SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL and OPENCV brought to one canonical record; undistortion by a guarded Newton iteration in
+ * fp64.  Bit-exact against the host build (csrc/host/camera_host.cpp) and from run to run.  pycolmap parity is UNPINNED.
+ *   gf_undistort_points
+ *     pts: fp32 point list, row i at pts + pts_stride * i (x, y; pts_stride >= 2: 2 for an [P,2] list, 4 for one side of an [M,4] match
+ *     block read in place), P rows cut into S segments by seg_offsets int32 [S+1] (ascending, from 0 to P); segment s belongs to camera
+ *     seg_camera[s] (int32 [S]) of cameras fp64 [C,8] = fx, fy, cx, cy, k1, k2, p1, p2.
+ *     out fp32 [P,2]: the ideal pixel, each coordinate rounded once to fp32; a camera without distortion passes the input bits through.
+ *     status uint8 [P]: 0 fine, 1 non-finite input, 2 no pre-image found, 3 the row lies in no segment or its camera index is outside
+ *     [0, C); on status != 0 both coordinates are NaN.  flags int32 [2], zeroed by the caller, only ever set to 1: [0] seg_offsets is not
+ *     an ascending list from 0 to P, [1] a camera index outside the table.  P < 0, S < 0, C < 0, and with P > 0: S == 0, C == 0,
+ *     pts_stride < 2 or a null pointer are GF_ERR_INVALID_ARGUMENT; P == 0 enqueues nothing.  One launch, no workspace.
+ *   gf_distort_points
+ *     The same arguments; out is the real-image pixel of an ideal pixel (closed form), status (may be NULL) 0, 1 or 3.
+ * ------------------------------------------------------------------------------------------ */
+int gf_undistort_points(const float* pts, long pts_stride, int P, const int32_t* seg_offsets, const int32_t* seg_camera, int S,
+                        const double* cameras, int C, float* out, uint8_t* status, int32_t* flags, void* stream);
+int gf_distort_points(const float* pts, long pts_stride, int P, const int32_t* seg_offsets, const int32_t* seg_camera, int S,
+                      const double* cameras, int C, float* out, uint8_t* status, int32_t* flags, void* stream);
 
 #ifdef __cplusplus
 }
