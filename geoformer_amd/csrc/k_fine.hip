@@ -265,6 +265,11 @@ __global__ __launch_bounds__(256) void fine_match(FmArgs a) {
 // operand by sqrt(C)): 249 us -> HBM time per 8-pair call at the nominal load.
 template <typename T>
 __global__ __launch_bounds__(256) void fine_match_mfma(FmArgs a) {
+    // No contraction in this kernel: the maxima below are taken over the ROUNDED products acc * scale2, and with contraction the compiler
+    // forms the exponents as fma(acc, scale2, -max) from the unrounded ones - at the maximum itself that is the product's rounding residual
+    // instead of 0, up to half an ulp of the logit (3e-5 at 500 log2 units): probabilities above 1 (confidences up to 1.00002 were seen in
+    // saturated windows) and saturated cells that are no longer equal, so that the first-index rule picked by residual.
+#pragma clang fp contract(off)
     using Mm = Mma32<T>;
     using Frag = typename Mm::Frag;
     const int lane = threadIdx.x & 63, h = lane >> 5, lr = lane & 31, m = blockIdx.x * 4 + (threadIdx.x >> 6);
