@@ -191,6 +191,13 @@ SIGNATURES = {
                                      c_size_t, c_void_p]),
     'gf_undistort_points': (c_int, [c_void_p, c_long, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'gf_distort_points': (c_int, [c_void_p, c_long, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'gf_relpose_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'gf_relpose_ransac': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_float, c_float, c_int, c_uint32, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'gf_relpose_lo_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'gf_relpose_ransac_lo': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_float, c_float, c_int, c_uint32, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t,
+                                     c_void_p]),
 }
 
 

@@ -29,6 +29,7 @@ TRI_HOST_LIB = os.path.join(OBJ, 'libtri_host.so')
 COVIS_HOST_LIB = os.path.join(OBJ, 'libcovis_host.so')
 BA_HOST_LIB = os.path.join(OBJ, 'libba_host.so')
 CAMERA_HOST_LIB = os.path.join(OBJ, 'libcamera_host.so')
+RELPOSE_HOST_LIB = os.path.join(OBJ, 'librelpose_host.so')
 
 
 def _headers_digest():
@@ -148,6 +149,14 @@ def build_camera_host(verbose=True):
                            (os.path.join(CSRC, 'camera_spec.h'),), verbose)
 
 
+def build_relpose_host(verbose=True):
+    """TEST INFRASTRUCTURE: the serial host form of the calibrated two-view RANSAC (csrc/host/relpose_host.cpp over csrc/rel_solver.h, the
+    text k_relpose.hip compiles for the device).  Only tests load it."""
+    return _build_host_lib(RELPOSE_HOST_LIB, 'relpose_host.stamp', os.path.join(CSRC, 'host', 'relpose_host.cpp'),
+                           tuple(os.path.join(CSRC, h) for h in ('rel_solver.h', 'pose_solver.h', 'fund_solver.h', 'solver_common.h',
+                                                                 'keypoint_spec.h', 'gf_hash.h')), verbose)
+
+
 def build(verbose=True, jobs=4):
     os.makedirs(OBJ, exist_ok=True)
     build_camera_host(verbose)
@@ -159,6 +168,7 @@ def build(verbose=True, jobs=4):
     build_tri_host(verbose)
     build_covis_host(verbose)
     build_ba_host(verbose)
+    build_relpose_host(verbose)
     srcs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.hip'))
     hdig = _headers_digest()
     with ThreadPoolExecutor(jobs) as ex:

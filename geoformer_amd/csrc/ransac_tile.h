@@ -1,9 +1,10 @@
 // The RANSAC around the minimal solvers, stated once for k_ransac.hip (homography), k_pose.hip (essential matrix), k_fundamental.hip
-// (fundamental matrix) and k_abspose.hip (absolute pose).  Device only: the host builds keep their own serial loops (host/pose_host.cpp,
-// host/fund_host.cpp, host/abspose_host.cpp, oracle/ransac_oracle.c), the independent statements the kernels are tested against bit for bit.
+// (fundamental matrix), k_abspose.hip (absolute pose) and k_relpose.hip (essential matrix for the pairs of a match list).  Device only: the
+// host builds keep their own serial loops (host/pose_host.cpp, host/fund_host.cpp, host/abspose_host.cpp, host/relpose_host.cpp,
+// oracle/ransac_oracle.c), the independent statements the kernels are tested against bit for bit.
 //
-// k_fundamental.hip and k_abspose.hip are this file's four stages - rt_prepare, rt_score, rt_final, rt_refit, launched by rt_run - over a
-// Model each; k_ransac.hip, k_pose.hip and k_triangulate.hip use the helpers only.
+// k_fundamental.hip, k_abspose.hip and k_relpose.hip are this file's stages - rt_prepare, rt_score, rt_final, rt_refit, and for
+// k_relpose.hip rt_pose, launched by rt_run - over a Model each; k_ransac.hip, k_pose.hip and k_triangulate.hip use the helpers only.
 //
 //   rt_counts_range   a pair's slice of a match list addressed by a device-side counts array, clamped to the buffers' capacity.
 //   rt_key            the selection rule "most inliers, then the smallest hypothesis" as one integer: count * 2^32 + (2^31 - 1 - hypothesis),
@@ -26,7 +27,8 @@
 //                     - per hypothesis the best root (most inliers, then the smallest root), then the block's best hypothesis by rt_key,
 //                       written with its solution to the block's slot of RtBlocks.
 //                     k_pose.hip's pose_score is the same stage written out with per-hypothesis results: on this kernel's per-block
-//                     winners it measured 1 - 3.5 % slower (profiles/ransac_tile.txt).
+//                     winners it measured 1 - 3.5 % slower (profiles/ransac_tile.txt).  k_relpose.hip runs the same solver through this
+//                     kernel at HYP = 32: 0.991 of pose_score + pose_final (0.976 .. 1.012, profiles/relative_pose.txt), inside the spread.
 //
 // The stages around rt_score, for problems addressed by an offsets array [N + 1] in device memory (gs_offsets_range of solver_common.h: a
 // block reads its two entries, clamped before anything is indexed with them).  Grid N, 256 threads, one workgroup a problem:
@@ -43,13 +45,16 @@
 //                     current and the candidate set over the SURVIVING rows live in the workspace, one byte per row each, and change
 //                     places when a candidate is accepted.  The last pass writes the model's outputs, n_inliers and the mask at the
 //                     surviving rows (filtered rows stay 0 from rt_final) - nothing when no round was accepted - and rounds[n].
+//   rt_pose<Model>    launched only for a model that declares the hook `pose`, between rt_final and rt_refit: what the model derives from the
+//                     winner with the whole workgroup (k_relpose.hip: the pose of an essential matrix by the inliers' votes), and where
+//                     that fails the withdrawal of valid, mask and outputs.  The other models launch exactly what they launched before.
 //   rt_block_sums<NS> for Model::fit: the block sum of NS per-thread partials with the bits of fs_refit_tree.
 //   rt_run<Model>     the entry point: the argument checks under the caller's name, the workspace carved, the launches between
 //                     gf_prof_begin / gf_prof_end, rounds = 0 when nothing was refitted.
 //
 // A Model is a plain struct with the types Args (the kernels' argument; the members rt_run and the stages name: offsets, N, M, thr2, rows,
 // use, norm, blk, valid, n_inliers, best, inliers, refit_rounds, set[2], rounds), Row and Cand (a refit's model), the constants HYP
-// (hypotheses per workgroup, a multiple of 4, at most 256), ROOTS (solutions per hypothesis at most), WS, OFF_SOL (where solve leaves
+// (hypotheses per workgroup, 64 or 32: iters is a multiple of 64 for every model), ROOTS (solutions per hypothesis at most), WS, OFF_SOL (where solve leaves
 // solution r: 9 doubles at OFF_SOL + 9 r), BOX, NORM (doubles of norm per problem), MIN_INLIERS, MAX_ROUNDS, and the __forceinline__ hooks
 //     void bind(const Args&, int n, int off)                 problem n's slices of the inputs, its first row being off; reads no workspace
 //     int  init(const Args&, int n)                          bind, and what prepare left; returns the number of rows to score, 0 when the
@@ -67,6 +72,9 @@
 //     int  original_inlier(const double (&S)[9], int i) const          row_valid and the predicate, on original row i
 //     void write_invalid(const Args&, int n) const           the model's outputs for "no solution"
 //     void write_solution(const Args&, int n, const double (&S)[9]) const
+//   rt_pose (optional)
+//     void pose(const Args&, int n, int len) const           block-cooperative: all 256 threads call it for problem n of len original rows
+//                                                            behind rt_final's outputs; its own LDS, its own barriers
 //   rt_refit
 //     Cand load_winner(const Args&, int n) const             what rt_final wrote, as a Cand
 //     int  fit(const uint8_t* cur, int cnt, Cand& c) const   block-cooperative: all 256 threads call it with c = the current model and
@@ -393,7 +401,23 @@ __global__ __launch_bounds__(256) void rt_refit(typename Model::Args a) {
     if (t == 0) a.rounds[n] = rounds;
 }
 
-// ---- the entry point around the four launches
+// a model with the hook `pose` gets one more launch between rt_final and rt_refit
+template <class Model, class = void>
+struct rt_has_pose { static constexpr bool value = false; };
+template <class Model>
+struct rt_has_pose<Model, decltype((void)&Model::pose)> { static constexpr bool value = true; };
+
+template <class Model>
+__global__ __launch_bounds__(256) void rt_pose(typename Model::Args a) {
+    const int n = blockIdx.x;
+    int off, len;
+    gs_offsets_range(a.offsets, n, a.M, off, len);
+    Model md;
+    md.init(a, n);
+    md.pose(a, n, len);
+}
+
+// ---- the entry point around the launches
 
 #define RT_CHECK_ARG(cond, msg)                                   \
     do {                                                          \
@@ -410,13 +434,15 @@ __global__ __launch_bounds__(256) void rt_refit(typename Model::Args a) {
 template <class Model>
 static int rt_run(const char* name, const char* tag, typename Model::Args& a, bool pointers, float pixel_thr, int iters, bool refit,
                   int refit_rounds, void* workspace, size_t workspace_bytes, size_t need, void* stream) {
-    static_assert(Model::HYP == 64 && Model::MAX_ROUNDS == 8, "the messages below name both numbers");
+    static_assert((Model::HYP == 64 || Model::HYP == 32) && Model::MAX_ROUNDS == 8, "the messages below name these numbers");
     const int N = a.N, M = a.M;
     RT_CHECK_ARG(pointers, "null pointer");
     RT_CHECK_ARG(M >= 0, "need M >= 0");
-    RT_CHECK_ARG(iters > 0 && iters % Model::HYP == 0, "iters must be a positive multiple of 64 (the hypotheses of one workgroup)");
+    RT_CHECK_ARG(iters > 0 && iters % 64 == 0, Model::HYP == 64 ? "iters must be a positive multiple of 64 (the hypotheses of one workgroup)"
+                                                                 : "iters must be a positive multiple of 64 (two workgroups of 32 hypotheses)");
     RT_CHECK_ARG(N > 0 && (long long)N * (iters / Model::HYP) <= RT_MAX_BLOCKS,
-                 "N out of range: need N > 0 and N * (iters / 64) <= 16777216 workgroups in one launch");
+                 Model::HYP == 64 ? "N out of range: need N > 0 and N * (iters / 64) <= 16777216 workgroups in one launch"
+                                  : "N out of range: need N > 0 and N * (iters / 32) <= 16777216 workgroups in one launch");
     RT_CHECK_ARG(pixel_thr > 0.f && pixel_thr < INFINITY, "pixel_thr must be positive and finite");
     RT_CHECK_ARG(!refit || (refit_rounds >= 0 && refit_rounds <= Model::MAX_ROUNDS), "refit_rounds must be 0 .. 8");
     if (workspace == nullptr || workspace_bytes < need) {
@@ -438,6 +464,7 @@ static int rt_run(const char* name, const char* tag, typename Model::Args& a, bo
     rt_prepare<Model><<<N, 256, 0, st>>>(a);
     rt_score<Model><<<(unsigned)N * a.blk.nblk, 256, 0, st>>>(a);
     rt_final<Model><<<N, 256, 0, st>>>(a);
+    if constexpr (rt_has_pose<Model>::value) rt_pose<Model><<<N, 256, 0, st>>>(a);
     if (a.refit_rounds > 0) rt_refit<Model><<<N, 256, 0, st>>>(a);
     gf_prof_end(tag, tok, st);
     if (refit && a.refit_rounds == 0 && hipMemsetAsync(a.rounds, 0, (size_t)N * sizeof(int32_t), st) != hipSuccess) {

@@ -568,6 +568,72 @@ def verify_matches(pairs, results, thr=1.0, min_inliers=15, sc_thres=0.25, iters
 
 
 # ---------------------------------------------------------------------------------------------
+# calibrated two-view verification: an essential-matrix RANSAC with pose recovery per pair, all pairs in one call on the device
+# ---------------------------------------------------------------------------------------------
+class RelativePoses(NamedTuple):
+    E: np.ndarray            # [P, 3, 3] float64, x1^T E x0 = 0 in normalised coordinates, Frobenius norm 1 (zeros where no pose was found)
+    R: np.ndarray            # [P, 3, 3] float64, x1 ~ R x0 + t
+    t: np.ndarray            # [P, 3] float64, unit length (the scale of a relative pose is not observable)
+    n_inliers: np.ndarray    # [P] int32
+    verified: np.ndarray     # [P] bool: a pose was found and it has at least min_inliers inliers
+    masks: list              # per pair: [n_p] bool, the inliers of a verified pair; all False otherwise
+    rounds: np.ndarray       # [P] int32: refits on the inliers accepted per pair (zeros without refit)
+
+
+def relative_poses(pairs, results, intrinsics, thr=1.0, min_inliers=15, sc_thres=0.25, iters=None, device='cuda', refit=0):
+    """The relative pose of every pair from its matches, for image sets with known intrinsics: where K is known a fundamental matrix is
+    the wrong model - two degrees of freedom too many, and no R, t.  Per pair an essential-matrix RANSAC with pose recovery
+    (ops.ransac_relative_pose: rows scoring below sc_thres or not finite take no part, five-point hypotheses on normalised coordinates,
+    squared Sampson distance below (thr / mean focal length)^2, the pose by the inliers' cheirality votes; the rule is
+    csrc/rel_solver.h) - one upload, four launches for all pairs, one read back.  intrinsics[path]: 3 x 3 K of the image, in the pixels of
+    the matches (what localize_queries takes and undistort_results returns); a pair whose image has no entry is a ValueError.
+    verified[p] = a pose was found and n_inliers[p] >= min_inliers; verified and masks mean what they mean in VerifiedMatches, so
+    consolidate_matches(..., keep=rp.masks) works unchanged.  refit = R in 1 .. 8: one more launch refits every pose on its inliers up to
+    R times (Gauss-Newton on the Sampson residual over R and unit t, inliers selected again; never fewer inliers than before); E, R, t,
+    n_inliers, verified and masks are then the refined model's and rounds counts the accepted refits.  On a purely planar scene the
+    essential matrix has a twin solution and either may be returned; there is no homography model test.  pairs / results as
+    consolidate_matches takes them."""
+    pairs = [tuple(p) for p in pairs]
+    if len(pairs) != len(results):
+        raise ValueError(f'relative_poses: {len(pairs)} pairs but {len(results)} results')
+    for p in pairs:
+        for path in p:
+            if path not in intrinsics:
+                raise ValueError(f'relative_poses: no intrinsics for {path!r}')
+    P = len(results)
+    ms = [np.asarray(r[0], dtype=np.float32).reshape(-1, 4) for r in results]
+    ss = [np.asarray(r[3], dtype=np.float32).reshape(-1) for r in results]
+    if any(len(m) != len(x) for m, x in zip(ms, ss)):
+        raise ValueError('relative_poses: a result whose matches and scores differ in length')
+    if P == 0:
+        return RelativePoses(np.zeros((0, 3, 3)), np.zeros((0, 3, 3)), np.zeros((0, 3)), np.zeros(0, np.int32), np.zeros(0, bool), [],
+                             np.zeros(0, np.int32))
+    Ks = np.stack([np.stack([np.asarray(intrinsics[path], dtype=np.float32).reshape(9) for path in p]) for p in pairs])      # [P, 2, 9]
+    offsets = np.concatenate([[0], np.cumsum([len(m) for m in ms])]).astype(np.int32)
+    M = int(offsets[-1])
+    block = np.concatenate([a.reshape(-1).view(np.int32) for a in (*ms, *ss, offsets, Ks[:, 0], Ks[:, 1])])
+    with torch.cuda.device(device):
+        d = torch.from_numpy(block).to(device)
+        k = d[5 * M + P + 1:].view(torch.float32)
+        rs = ops.ransac_relative_pose(d[:4 * M].view(torch.float32).view(M, 4), d[4 * M:5 * M].view(torch.float32), d[5 * M:5 * M + P + 1], P,
+                                      k[:9 * P].view(P, 3, 3), k[9 * P:].view(P, 3, 3), pixel_thr=thr, sc_thres=sc_thres,
+                                      iters=ops.REL_RANSAC_ITERS if iters is None else iters, refit=refit)
+        if not refit:
+            rs['rounds'] = torch.zeros(P, dtype=torch.int32, device=rs['valid'].device)
+        out = torch.cat([rs[q].reshape(-1).view(torch.uint8) for q in ('E', 'R', 't', 'valid', 'n_inliers', 'rounds', 'inliers')]).cpu().numpy()
+    E = out[:72 * P].view(np.float64).reshape(P, 3, 3).copy()
+    R = out[72 * P:144 * P].view(np.float64).reshape(P, 3, 3).copy()
+    t = out[144 * P:168 * P].view(np.float64).reshape(P, 3).copy()
+    valid = out[168 * P:172 * P].view(np.int32)
+    nin = out[172 * P:176 * P].view(np.int32).copy()
+    rounds = out[176 * P:180 * P].view(np.int32).copy()
+    inl = out[180 * P:].astype(bool)
+    verified = (valid == 1) & (nin >= min_inliers)
+    masks = [inl[offsets[p]:offsets[p + 1]].copy() if verified[p] else np.zeros(len(ms[p]), bool) for p in range(P)]
+    return RelativePoses(E, R, t, nin, verified, masks, rounds)
+
+
+# ---------------------------------------------------------------------------------------------
 # localisation: a camera pose per query from its matches against database images with known 3-D points, all queries in one call
 # ---------------------------------------------------------------------------------------------
 class LocalizedQueries(NamedTuple):
@@ -1433,7 +1499,8 @@ def estimate_homography(matches, thr, device='cuda'):
 
 def estimate_relative_pose(matches, K0, K1, thr=0.5, device='cuda'):
     """Essential-matrix RANSAC + pose recovery from [n,4] pixel matches on the device (estimate_pose of the reference's metrics.py);
-    returns (R, t, inlier mask) or None."""
+    returns (R, t, inlier mask) or None.  One pair per call, for the validation metrics; for the pairs of a match list - all in one
+    call, with the row filter of consolidate_matches and an optional refit on the inliers - see relative_poses."""
     if len(matches) < 5:
         return None
     m = torch.as_tensor(np.asarray(matches), dtype=torch.float32, device=device)
@@ -1614,6 +1681,11 @@ def build_parser():
     q.add_argument('--verify-refit', type=int, nargs='?', const=4, default=0, metavar='R',
                    help='with --verify: refit every pair\'s model on its inliers up to R times (1 .. 8; the bare flag: 4) and select the inliers '
                         'again; each .npz of --out and two_view.npz gain refit_rounds')
+    q.add_argument('--verify-pose', action='store_true',
+                   help='verify every pair with known intrinsics (essential-matrix RANSAC with pose recovery on the device; needs --intrinsics or '
+                        '--cameras, not with --verify; reuses --verify-thr, --min-inliers and --verify-refit): each .npz of --out gains E, R, t, '
+                        'inliers and verified; with --keypoints only the inliers of verified pairs are consolidated and two_view.npz holds the poses')
+    q.add_argument('--intrinsics', metavar='FILE', default=None, help='with --verify-pose: one line per image: path fx fy cx cy')
     loc = sub.add_parser('localize', help='camera poses of query images from their matches against database images with 3-D maps')
     loc.add_argument('list', help='text file with `query database` image paths per line (relative paths: relative to the file)')
     loc.add_argument('--xyz', metavar='DIR', required=True,
@@ -1822,6 +1894,18 @@ def _cameras_for(path, pairs):
     return out
 
 
+def _intrinsics_for(path, pairs):
+    """read_intrinsics(path) keyed by the image names of `pairs`: a name is looked up as the pair list has it, then as an absolute path."""
+    intr = read_intrinsics(path)
+    out = {}
+    for name in {n for p in pairs for n in p}:
+        full = os.path.abspath(name)
+        if name not in intr and full not in intr:
+            raise SystemExit(f'{path}: no intrinsics for {name!r}')
+        out[name] = intr[name] if name in intr else intr[full]
+    return out
+
+
 def main(argv=None):
     """`python -m geoformer_amd.matcher match|hpatches|pairs|localize|triangulate|refine|localize-sparse ...` (arguments: build_parser)."""
     ap = build_parser()
@@ -1847,6 +1931,13 @@ def main(argv=None):
             ap.error('localize-sparse: need --refit 0 .. 8 and --thr > 0')
         run_localize_sparse(args)
         return
+    if args.cmd == 'pairs' and args.verify_pose:
+        if args.verify:
+            ap.error('pairs: --verify-pose may not be combined with --verify')
+        if (args.intrinsics is None) == (args.cameras is None):
+            ap.error('pairs: --verify-pose needs --intrinsics FILE or --cameras FILE (one of them)')
+        if not 0 <= args.verify_refit <= 8 or not args.verify_thr > 0:
+            ap.error('pairs: --verify-pose needs --verify-refit 0 .. 8 and --verify-thr > 0')
     world = int(os.environ.get('WORLD_SIZE', '1'))
     local = int(os.environ.get('LOCAL_RANK', '0'))
     if world > 1:
@@ -1870,13 +1961,17 @@ def main(argv=None):
                   f"camera model's range (dropped downstream)")
         vm = (verify_matches(pairs, results, args.verify_thr, args.min_inliers, args.sc_thres, device=matcher.device, refit=args.verify_refit)
               if args.verify else None)
+        if args.verify_pose:
+            vm = relative_poses(pairs, results, intr if intr is not None else _intrinsics_for(args.intrinsics, pairs), args.verify_thr, args.min_inliers, args.sc_thres, device=matcher.device, refit=args.verify_refit)
         refit = {} if vm is None or not args.verify_refit else {'refit_rounds': vm.rounds}
+        model = {} if vm is None else {'E': vm.E, 'R': vm.R, 't': vm.t} if args.verify_pose else {'F': vm.F}
         if args.out:
             os.makedirs(args.out, exist_ok=True)
         for k, ((p0, p1), res) in enumerate(zip(pairs, results)):
             if args.out:
                 stem = '_'.join(os.path.splitext(os.path.basename(p))[0] for p in (p0, p1))
-                extra = {} if vm is None else {'F': vm.F[k], 'inliers': vm.masks[k], 'verified': vm.verified[k], **{q: v[k] for q, v in refit.items()}}
+                extra = {} if vm is None else {**{q: v[k] for q, v in model.items()}, 'inliers': vm.masks[k], 'verified': vm.verified[k],
+                                               **{q: v[k] for q, v in refit.items()}}
                 np.savez(os.path.join(args.out, f'{k:05d}_{stem}.npz'), matches=res[0], kpts1=res[1], kpts2=res[2], scores=res[3], **extra)
         if vm is not None:
             print(f'{int(vm.verified.sum())} of {len(pairs)} pairs verified (thr {args.verify_thr} px, at least {args.min_inliers} inliers), '
@@ -1889,7 +1984,8 @@ def main(argv=None):
             if intr is not None:
                 write_intrinsics(os.path.join(args.keypoints, 'intrinsics.txt'), intr, cm.names)
             if vm is not None:
-                np.savez(os.path.join(args.keypoints, 'two_view.npz'), pairs=cm.pair_images, F=vm.F, n_inliers=vm.n_inliers, verified=vm.verified, **refit)
+                np.savez(os.path.join(args.keypoints, 'two_view.npz'), pairs=cm.pair_images, **model, n_inliers=vm.n_inliers, verified=vm.verified,
+                         **refit)
             print(f'{len(cm.names)} images, {sum(len(k) for k in cm.keypoints)} keypoints, {sum(len(m) for m in cm.matches)} matches as keypoint '
                   f'indices -> {args.keypoints}')
         st = matcher.store

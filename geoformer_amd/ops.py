@@ -575,6 +575,59 @@ def ransac_fundamental(matches, scores, offsets, N, pixel_thr=1.0, sc_thres=0.25
     return {'F': F, 'valid': valid, 'n_inliers': nin, 'inliers': inl[:M], 'hypothesis': best}
 
 
+REL_RANSAC_ITERS = 512          # fixed, not adaptive; a positive multiple of 64.  An all-inlier sample of 5 at 50 % outliers: 1 - 1e-7 of the pairs
+
+
+def ransac_relative_pose(matches, scores, offsets, N, K0, K1, pixel_thr=1.0, sc_thres=0.25, iters=REL_RANSAC_ITERS, seed=RANSAC_SEED, refit=0):
+    """Device essential-matrix RANSAC with pose recovery for the N pairs of a match list (csrc/rel_solver.h): two-view verification with
+    known intrinsics.  matches fp32 [M,4] pixel rows (x0, y0, x1, y1) sorted by pair, scores fp32 [M] or None, offsets int32 [N+1] on the
+    device, K0 / K1 [N,3,3] (or [3,3] for all).  A row takes part iff it is finite and (with scores) scores >= sc_thres; a pair is estimated
+    iff 5 rows take part and its focal lengths are finite and positive.  Five-point hypotheses, squared Sampson distance in normalised
+    coordinates below (pixel_thr / mean focal)^2.  Returns dict(E fp64 [N,3,3] of Frobenius norm 1, R fp64 [N,3,3], t fp64 [N,3] unit with
+    x1 ~ R x0 + t, valid int32 [N], n_inliers int32 [N], n_cheiral int32 [N], inliers uint8 [M], hypothesis int32 [N,2]).
+    refit = R in 1 .. 8: the pose is refitted on its inliers up to R times (three Gauss-Newton steps on the signed Sampson residual over
+    (R, unit t), inliers selected again; a candidate with fewer inliers is never taken - step 7 of csrc/rel_solver.h, one more launch);
+    E = [t]x R, R, t, n_inliers and inliers are then the refined model's, hypothesis still names the five-point model that seeded it, and
+    the dict gains rounds int32 [N], the refits accepted per pair (0: the pair's outputs are the five-point winner's bits)."""
+    _need_cuda(matches, offsets)
+    dev = matches.device
+    M = matches.shape[0]
+    m = _contig(matches.float().reshape(M, 4)) if M else torch.zeros(1, 4, dtype=torch.float32, device=dev)
+    sc = None if scores is None or M == 0 else _contig(scores.float())
+    off = _contig(offsets.to(device=dev, dtype=torch.int32))
+    if off.numel() != N + 1:
+        raise ValueError(f'ransac_relative_pose: offsets has {off.numel()} entries for N = {N}')
+    rows = max(N, 1)                # (N <= 0 is the entry point's error to report: it gets real pointers)
+    ks = []
+    for K in (K0, K1):
+        Kt = torch.as_tensor(K, dtype=torch.float32, device=dev)
+        ks.append(_contig((Kt.reshape(1, 9).expand(rows, 9) if Kt.numel() == 9 else Kt.reshape(rows, 9)).clone()))
+    E = torch.empty(rows, 3, 3, dtype=torch.float64, device=dev)
+    R = torch.empty(rows, 3, 3, dtype=torch.float64, device=dev)
+    t = torch.empty(rows, 3, dtype=torch.float64, device=dev)
+    valid = torch.empty(rows, dtype=torch.int32, device=dev)
+    nin = torch.empty(rows, dtype=torch.int32, device=dev)
+    nch = torch.empty(rows, dtype=torch.int32, device=dev)
+    best = torch.empty(rows, 2, dtype=torch.int32, device=dev)
+    inl = torch.zeros(max(M, 1), dtype=torch.uint8, device=dev)
+    out = {'E': E, 'R': R, 't': t, 'valid': valid, 'n_inliers': nin, 'n_cheiral': nch, 'inliers': inl[:M], 'hypothesis': best}
+    L_ = _lib.lib()
+    if refit:
+        rounds = torch.empty(rows, dtype=torch.int32, device=dev)
+        ws = _ws.get('relpose_lo', L_.gf_relpose_lo_workspace_bytes(N, M, max(int(iters), 1)), dev)
+        check(L_.gf_relpose_ransac_lo(_p(m), _p(sc), _p(off), N, M, _p(ks[0]), _p(ks[1]), float(sc_thres), float(pixel_thr), int(iters), int(seed),
+                                      _p(E), _p(R), _p(t), _p(valid), _p(nin), _p(nch), _p(best), _p(inl), int(refit), _p(rounds), _p(ws),
+                                      ws.numel(), _stream()),
+              'gf_relpose_ransac_lo')
+        out['rounds'] = rounds
+        return out
+    ws = _ws.get('relpose', L_.gf_relpose_workspace_bytes(N, M, max(int(iters), 1)), dev)
+    check(L_.gf_relpose_ransac(_p(m), _p(sc), _p(off), N, M, _p(ks[0]), _p(ks[1]), float(sc_thres), float(pixel_thr), int(iters), int(seed), _p(E),
+                               _p(R), _p(t), _p(valid), _p(nin), _p(nch), _p(best), _p(inl), _p(ws), ws.numel(), _stream()),
+          'gf_relpose_ransac')
+    return out
+
+
 ABS_RANSAC_ITERS = 512          # fixed, not adaptive; a positive multiple of 64.  An all-inlier sample of 3 at 70 % outliers: 1 - 1e-6 of the queries
 
 

@@ -42,7 +42,7 @@ typedef enum { GF_F32 = 0, GF_F16 = 1, GF_BF16 = 2 } gf_dtype;
  * Likewise with the gf_keypoint_* entries, gf_fundamental_* (gf_fundamental_ransac_lo and its workspace query included), gf_linear_rows,
  * gf_index_rows, gf_fine_rows*, gf_abspose_* and gf_xyz_lookup (with gf_xyz_map), gf_track_link, gf_track_flatten and gf_triangulate*,
  * gf_covis_cluster, gf_sparse_rows and gf_covis_select, gf_bundle_workspace_bytes and gf_bundle_adjust, gf_bundle_pcg_workspace_bytes and gf_bundle_adjust_pcg,
- * gf_undistort_points and gf_distort_points. */
+ * gf_undistort_points and gf_distort_points, gf_relpose_* (four entries). */
 #define GF_ABI_VERSION 4
 int gf_abi_version(void);
 const char* gf_last_error(void);
@@ -961,6 +961,43 @@ int gf_undistort_points(const float* pts, long pts_stride, int P, const int32_t*
                         const double* cameras, int C, float* out, uint8_t* status, int32_t* flags, void* stream);
 int gf_distort_points(const float* pts, long pts_stride, int P, const int32_t* seg_offsets, const int32_t* seg_camera, int S,
                       const double* cameras, int C, float* out, uint8_t* status, int32_t* flags, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Calibrated two-view verification: essential-matrix RANSAC with pose recovery for every pair of a match list, where intrinsics are known
+ * (the offsets layout, the row filter and the refit contract of gf_fundamental_ransac*; the solver, the inlier test and the pose recovery
+ * of gf_pose_essential_ransac).  The rule is geoformer_amd/csrc/rel_solver.h, which also compiles for the host
+ * (csrc/host/relpose_host.cpp): bit-exact against that build and from run to run.  OpenCV parity is UNPINNED.  Profiler tag "rel_ransac".
+ *   gf_relpose_ransac
+ *     matches fp32 [M,4] (x0, y0, x1, y1 in pixels), scores fp32 [M] or NULL, offsets int32 [N + 1] in DEVICE memory (entries are clamped into
+ *     [0, M] before use), K0, K1 fp32 [N,9] row-major intrinsics of the pair's two images.  A row takes part iff its four coordinates are finite
+ *     and, with scores, its score is not NaN and >= sc_thres.  Coordinates are normalised by K; pixel_thr is divided by the mean focal length
+ *     (ps_threshold).  A pair is estimated iff at least 5 rows take part and K0[0], K0[4], K1[0], K1[4] are finite and positive.
+ *     iters: FIXED number of five-point hypotheses per pair, a positive multiple of 64; hypothesis t of pair n draws its rows from (seed, n, t).
+ *     N > 0 and N * (iters / 32) <= 16777216 (the workgroups of one launch), pixel_thr positive and finite; anything else is
+ *     GF_ERR_INVALID_ARGUMENT, never wrapped.
+ *     outputs: E fp64 [N,9] (x1^T E x0 = 0 in normalised coordinates, Frobenius norm 1), R fp64 [N,9] and t fp64 [N,3] of unit length with
+ *     x1 ~ R x0 + t, valid int32 [N] (1 iff the winner has at least 5 inliers, E decomposes and a candidate pose has an inlier in front of
+ *     both cameras), n_inliers int32 [N], n_cheiral int32 [N] (the chosen candidate's votes), best int32 [N,2] (hypothesis, root; -1),
+ *     inliers uint8 [M] (squared Sampson distance in normalised coordinates < thr^2; filtered rows 0).  Not valid: zeros, best -1.
+ *     workspace: gf_relpose_workspace_bytes(N, M, iters) bytes.  Four launches, no host synchronisation.
+ *   gf_relpose_ransac_lo
+ *     followed by a refit of every pair's pose on its inliers (one more launch): up to refit_rounds times three Gauss-Newton steps on the
+ *     signed Sampson residual over (R, t) with |t| = 1, sums in a fixed order, the inliers selected again over all rows that take part, the
+ *     candidate accepted iff it has at least as many inliers; stops at a rejected candidate, a failed fit, an unchanged set or fewer than 6
+ *     inliers.  refit_rounds: 0 .. 8; 0 is exactly gf_relpose_ransac, with rounds all 0.  rounds int32 [N]: the refits accepted; 0 means the
+ *     five-point winner's bits.  After an accepted refit E = [t]x R scaled to norm 1.  n_inliers never decreases; best and n_cheiral keep
+ *     describing the seeding hypothesis.  workspace: gf_relpose_lo_workspace_bytes(N, M, iters) bytes.
+ * ------------------------------------------------------------------------------------------ */
+size_t gf_relpose_workspace_bytes(int N, int M, int iters);
+int gf_relpose_ransac(const float* matches, const float* scores, const int32_t* offsets, int N, int M, const float* K0, const float* K1,
+                      float sc_thres, float pixel_thr, int iters, uint32_t seed, double* E, double* R, double* t, int32_t* valid,
+                      int32_t* n_inliers, int32_t* n_cheiral, int32_t* best, uint8_t* inliers, void* workspace, size_t workspace_bytes,
+                      void* stream);
+size_t gf_relpose_lo_workspace_bytes(int N, int M, int iters);
+int gf_relpose_ransac_lo(const float* matches, const float* scores, const int32_t* offsets, int N, int M, const float* K0, const float* K1,
+                         float sc_thres, float pixel_thr, int iters, uint32_t seed, double* E, double* R, double* t, int32_t* valid,
+                         int32_t* n_inliers, int32_t* n_cheiral, int32_t* best, uint8_t* inliers, int refit_rounds, int32_t* rounds,
+                         void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
