@@ -588,6 +588,9 @@ extern "C" int gf_linear(const void* a1, long lda1, int k1, const void* a2, long
     GF_CHECK_ARG(N % 32 == 0, "N must be a multiple of 32");
     GF_CHECK_ARG(epilogue >= EPI_NONE && epilogue <= EPI_LN_RES, "unknown epilogue");
     GF_CHECK_ARG(rowgroup_bias == nullptr || rowgroup_rows > 0, "rowgroup_rows must be > 0");
+    // the epilogue reads a whole column tile of the row-group bias (128 or 256 entries), stored or not: a ragged last tile would read
+    // behind the row's end, in the last row group behind the table's
+    GF_CHECK_ARG(rowgroup_bias == nullptr || N % 128 == 0, "a row-group bias needs N to be a multiple of 128 (whole column tiles)");
     const int es = dtype == GF_F32 ? 4 : 2;
     GF_CHECK_ARG((lda1 * es) % 16 == 0 && (k2 == 0 || (lda2 * es) % 16 == 0), "operand rows must be 16-byte aligned");
     GF_CHECK_ARG((ldo * es) % 16 == 0 && (uintptr_t)out % 16 == 0, "output rows must be 16-byte aligned");
@@ -648,6 +651,7 @@ extern "C" int gf_linear_rows(const uint64_t* row_table, int row_align, const in
     GF_CHECK_ARG(N % 32 == 0, "N must be a multiple of 32");
     GF_CHECK_ARG(epilogue >= EPI_NONE && epilogue <= EPI_LN_RES, "unknown epilogue");
     GF_CHECK_ARG(rowgroup_bias == nullptr || rowgroup_rows > 0, "rowgroup_rows must be > 0");
+    GF_CHECK_ARG(rowgroup_bias == nullptr || N % 128 == 0, "a row-group bias needs N to be a multiple of 128 (whole column tiles)");   // as gf_linear
     GF_CHECK_ARG(row_align > 0 && (row_align & (row_align - 1)) == 0 && row_align % 16 == 0, "operand rows must be 16-byte aligned (row_align: a power of two >= 16)");
     GF_CHECK_ARG((uintptr_t)row_table % 8 == 0, "the row table must be 8-byte aligned");
     GF_CHECK_ARG(group_count == nullptr || (group_rows > 0 && group_count_stride >= 0), "group_rows must be > 0");

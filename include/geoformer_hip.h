@@ -325,7 +325,7 @@ int gf_conv3x3_nhwc(const void* x, const void* wstream, const float* shift, cons
  *   epilogue: 0 none, 1 ReLU, 2 Tanh, 3 LayerNorm(gamma, beta, eps) over N,
  *             4 residual + LayerNorm(...) with optional predicate row_flag[m / flag_rows]
  *               (0 -> out = residual: the GeoTransformer "layer skipped for this sample" case);
- *   LayerNorm epilogues need N in {128, 256}.
+ *   LayerNorm epilogues need N in {128, 256}; a rowgroup_bias needs N % 128 == 0 (its column tiles are read whole).
  * ------------------------------------------------------------------------------------------ */
 int gf_linear(const void* a1, long lda1, int k1, const void* a2, long lda2, int k2, const void* w,
               const float* bias, const void* rowgroup_bias, int rowgroup_rows, int epilogue,
