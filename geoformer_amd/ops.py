@@ -510,6 +510,21 @@ def _intrinsics(K, N, dev):
     return _contig(K.to(device=dev, dtype=torch.float32).reshape(N, 9))
 
 
+def _intrinsics_rows(K, rows, dev):
+    """K [rows,3,3], or one [3,3] for all -> a fresh contiguous fp32 [rows,9]."""
+    Kt = torch.as_tensor(K, dtype=torch.float32, device=dev)
+    return _contig((Kt.reshape(1, 9).expand(rows, 9) if Kt.numel() == 9 else Kt.reshape(rows, 9)).clone())
+
+
+def _scores_offsets(what, scores, offsets, M, N, dev):
+    """The row filter's scores (None without scores or rows) and the int32 [N+1] offsets of the N problems of a match list."""
+    sc = None if scores is None or M == 0 else _contig(scores.float())
+    off = _contig(offsets.to(device=dev, dtype=torch.int32))
+    if off.numel() != N + 1:
+        raise ValueError(f'{what}: offsets has {off.numel()} entries for N = {N}')
+    return sc, off
+
+
 def ransac_essential(mkpts0, mkpts1, counts, N, K0, K1, pixel_thr=0.5, iters=POSE_RANSAC_ITERS, seed=RANSAC_SEED):
     """Device essential-matrix RANSAC + pose recovery (metrics.py:72-98 without its cv2 host round trip).  mkpts0/mkpts1 fp32 [M,2] pixel
     keypoints sorted by pair, counts int32 [1+N] on the device, K0/K1 [N,3,3].  Returns dict(E fp64 [N,3,3] of Frobenius norm 1,
@@ -551,10 +566,7 @@ def ransac_fundamental(matches, scores, offsets, N, pixel_thr=1.0, sc_thres=0.25
     dev = matches.device
     M = matches.shape[0]
     m = _contig(matches.float().reshape(M, 4)) if M else torch.zeros(1, 4, dtype=torch.float32, device=dev)
-    sc = None if scores is None or M == 0 else _contig(scores.float())
-    off = _contig(offsets.to(device=dev, dtype=torch.int32))
-    if off.numel() != N + 1:
-        raise ValueError(f'ransac_fundamental: offsets has {off.numel()} entries for N = {N}')
+    sc, off = _scores_offsets('ransac_fundamental', scores, offsets, M, N, dev)
     F = torch.empty(N, 3, 3, dtype=torch.float64, device=dev)
     valid = torch.empty(N, dtype=torch.int32, device=dev)
     nin = torch.empty(N, dtype=torch.int32, device=dev)
@@ -593,15 +605,9 @@ def ransac_relative_pose(matches, scores, offsets, N, K0, K1, pixel_thr=1.0, sc_
     dev = matches.device
     M = matches.shape[0]
     m = _contig(matches.float().reshape(M, 4)) if M else torch.zeros(1, 4, dtype=torch.float32, device=dev)
-    sc = None if scores is None or M == 0 else _contig(scores.float())
-    off = _contig(offsets.to(device=dev, dtype=torch.int32))
-    if off.numel() != N + 1:
-        raise ValueError(f'ransac_relative_pose: offsets has {off.numel()} entries for N = {N}')
+    sc, off = _scores_offsets('ransac_relative_pose', scores, offsets, M, N, dev)
     rows = max(N, 1)                # (N <= 0 is the entry point's error to report: it gets real pointers)
-    ks = []
-    for K in (K0, K1):
-        Kt = torch.as_tensor(K, dtype=torch.float32, device=dev)
-        ks.append(_contig((Kt.reshape(1, 9).expand(rows, 9) if Kt.numel() == 9 else Kt.reshape(rows, 9)).clone()))
+    ks = [_intrinsics_rows(K, rows, dev) for K in (K0, K1)]
     E = torch.empty(rows, 3, 3, dtype=torch.float64, device=dev)
     R = torch.empty(rows, 3, 3, dtype=torch.float64, device=dev)
     t = torch.empty(rows, 3, dtype=torch.float64, device=dev)
@@ -647,13 +653,9 @@ def ransac_absolute_pose(p2d, p3d, scores, offsets, N, K, pixel_thr=12.0, sc_thr
     b = _contig(p3d.float().reshape(M, 3)) if M else torch.zeros(1, 3, dtype=torch.float32, device=dev)
     if p3d.shape[0] != M:
         raise ValueError(f'ransac_absolute_pose: {M} 2-D points but {p3d.shape[0]} 3-D points')
-    sc = None if scores is None or M == 0 else _contig(scores.float())
-    off = _contig(offsets.to(device=dev, dtype=torch.int32))
-    if off.numel() != N + 1:
-        raise ValueError(f'ransac_absolute_pose: offsets has {off.numel()} entries for N = {N}')
-    Kt = torch.as_tensor(K, dtype=torch.float32, device=dev)
-    k = _contig((Kt.reshape(1, 9).expand(max(N, 1), 9) if Kt.numel() == 9 else Kt.reshape(max(N, 1), 9)).clone())
+    sc, off = _scores_offsets('ransac_absolute_pose', scores, offsets, M, N, dev)
     rows = max(N, 1)                # (N <= 0 is the entry point's error to report: it gets real pointers)
+    k = _intrinsics_rows(K, rows, dev)
     R = torch.empty(rows, 3, 3, dtype=torch.float64, device=dev)
     t = torch.empty(rows, 3, dtype=torch.float64, device=dev)
     valid = torch.empty(rows, dtype=torch.int32, device=dev)

@@ -1,5 +1,5 @@
 """`python -m geoformer_amd.matcher refine` on written files, read back; matcher.refine's host side and write_poses.  No GPU: the device
-step (matcher._refine_device) is replaced by the host build of the same rule, which the GPU tests show to be bit-identical."""
+step (sfm._refine_device) is replaced by the host build of the same rule, which the GPU tests show to be bit-identical."""
 import os
 
 import numpy as np
@@ -10,8 +10,8 @@ import bundle_cases as bc
 
 @pytest.fixture()
 def planted(monkeypatch):
-    from geoformer_amd import matcher
-    monkeypatch.setattr(matcher, '_refine_device', bc.host_refine_device)
+    from geoformer_amd import matcher, sfm
+    monkeypatch.setattr(sfm, '_refine_device', bc.host_refine_device)
     s = bc.make_scene(21, n_cams=6, n_points=150, outliers=0.05)
     free = bc.free_flags(s)
     bc.keep_fixed_true(s, free)

@@ -1,5 +1,5 @@
 """`python -m geoformer_amd.matcher refine --solver pcg` on written files, and matcher.refine(solver='pcg')'s host side.  No GPU: the device
-step (matcher._refine_device) is replaced by the host build of the same rules, which the GPU tests show to be bit-identical."""
+step (sfm._refine_device) is replaced by the host build of the same rules, which the GPU tests show to be bit-identical."""
 import numpy as np
 import pytest
 
@@ -30,8 +30,8 @@ def scene130():
 
 @pytest.fixture()
 def planted(monkeypatch, scene130):
-    from geoformer_amd import matcher
-    monkeypatch.setattr(matcher, '_refine_device', pc.host_refine_device_pcg)
+    from geoformer_amd import matcher, sfm
+    monkeypatch.setattr(sfm, '_refine_device', pc.host_refine_device_pcg)
     return (matcher, scene130) + as_matcher_inputs(matcher, scene130)
 
 
@@ -55,8 +55,8 @@ def test_refine_with_pcg_takes_130_free_images_and_dense_names_the_limit(planted
 
 
 def test_the_dense_solver_still_returns_no_cg_log(monkeypatch):
-    from geoformer_amd import matcher
-    monkeypatch.setattr(matcher, '_refine_device', pc.host_refine_device_pcg)
+    from geoformer_amd import matcher, sfm
+    monkeypatch.setattr(sfm, '_refine_device', pc.host_refine_device_pcg)
     s = bc.make_scene(21, n_cams=6, n_points=150, outliers=0.05)
     bc.keep_fixed_true(s, bc.free_flags(s))
     cm, tt, intr, poses, fixed = as_matcher_inputs(matcher, s)
